@@ -23,7 +23,11 @@ rank fails or WORLD_SIZE disagrees with --gpus -- it never measures one GPU
 under an N-GPU label.
 
 Prints one JSON line (rank 0) with the driver contract fields plus
-`roofline` (dominant kernel vs HBM peak) and `cpu_baseline`.
+`roofline` (dominant kernel vs HBM peak, from the timed steps' own events)
+and `cpu_baseline`.  A plain run sets up, warms up, times the steps and
+prints; the CPU baseline is a run of its own on the host cores and is
+measured only with --full (null otherwise).  --dump-outputs DIR writes what
+the last timed step left, for comparing two builds output for output.
 """
 from __future__ import annotations
 
@@ -97,6 +101,33 @@ def bytes_per_colstep(precision: int, diag: bool) -> int:
     s = precision
     b = 2 * (56 * s + 4) + 6 * s + 6 * 4 + 12 * s
     return b + (16 * s if diag else 0)
+
+
+DUMP_COLS = 65536  # --dump-outputs: at most this many columns (fp64: 56 + 16 + 3 rows, 39 MB)
+
+
+def dump_outputs(path: str, cs, diag) -> None:
+    """--dump-outputs: what a caller of the timed path holds after its last
+    step -- the columns' state (56 rows), ISNOW and status, and `diag`, the 16
+    diagnostics of the last timed output step (None: no file) -- as
+    <path>/<name>.npy in the run's precision.  Of more than DUMP_COLS columns
+    a fixed seeded sample is written, its indices (into the order the GPU
+    holds, --order) in columns.npy."""
+    import torch
+    n = cs.ncol
+    idx = np.arange(n) if n <= DUMP_COLS else \
+        np.sort(np.random.default_rng(20240607).choice(n, DUMP_COLS, replace=False))
+    sel = torch.as_tensor(idx, device=cs.state.device)
+    ft = np.float32 if cs.state.dtype == torch.float32 else np.float64
+    os.makedirs(path, exist_ok=True)
+    out = {"columns": idx.astype(np.float64),
+           "state": cs.state[:, sel].cpu().numpy(),
+           "isnow": cs.isnow[sel].cpu().numpy().astype(ft),
+           "status": cs.status[sel].cpu().numpy().astype(ft)}
+    if diag is not None:
+        out["diag"] = diag[:, sel].cpu().numpy().astype(ft)
+    for name, v in out.items():
+        np.save(os.path.join(path, name + ".npy"), v)
 
 
 def workload_name(a, n: int) -> str:
@@ -176,8 +207,18 @@ def parse():
                     help="(under a launcher, world 1) issue the output-step collective even "
                          "though one rank has nothing to exchange: the RCCL code path's own "
                          "cost on the GPU (its copy kernels), measurable on one GPU")
-    ap.add_argument("--no-cpu-baseline", action="store_true")
+    ap.add_argument("--full", action="store_true",
+                    help="also measure what the headline figure does not need: the CPU baseline "
+                         "(`cpu_baseline`, the reference on the host cores, a run of its own "
+                         "before the GPU is touched); a plain run reports it as null")
+    ap.add_argument("--no-cpu-baseline", action="store_true",
+                    help="(with --full) leave the CPU baseline out")
     ap.add_argument("--cpu-steps", type=int, default=32)
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="after the timed steps, write what the last timed step left (rank 0's "
+                         "state, snow-layer counts, column status, and the diagnostics of the "
+                         "last timed output step) to DIR/<name>.npy, float32 or float64; of more "
+                         f"than {DUMP_COLS} columns a fixed seeded sample (DIR/columns.npy)")
     ap.add_argument("--launch-probe", action="store_true",
                     help="launcher check only (CPU tests): every rank joins the process group "
                          "over gloo and contributes its column count, rank 0 prints the line "
@@ -351,9 +392,9 @@ def main():
     if a.replicate > 1:
         cols = cols.take(np.tile(np.arange(ngen), a.replicate))
 
-    # ---- CPU baseline (rank 0, N=1), BEFORE anything touches the GPU ------
+    # ---- CPU baseline (--full; rank 0, N=1), BEFORE anything touches the GPU
     cpu = None
-    if world == 1 and not a.no_cpu_baseline:
+    if a.full and world == 1 and not a.no_cpu_baseline:
         sys.path.insert(0, os.path.join(ROOT, "oracle"))
         try:
             import cpu_baseline
@@ -383,9 +424,19 @@ def main():
     n = cs.ncol
     if a.forcing == "resident":
         F = torch.empty((a.period, L.NFORCING, n), dtype=dtype, device=dev)
-        for s in range(a.period):
-            F[s].copy_(torch.from_numpy(cases.forcing_step(
-                cols, (julian0 + s * a.dt / 86400.0) % yearlen, yearlen, s, seed=seed)))
+        # only the slices the run reads (step k reads slice k % period); each
+        # slice has its own generator, so a few host threads build them side
+        # by side, a batch at a time, with the same values as one by one
+        used = min(a.period, a.warmup + a.steps)
+        nthr = max(1, min(8, used, len(os.sched_getaffinity(0))))
+        from concurrent.futures import ThreadPoolExecutor
+        with ThreadPoolExecutor(nthr) as ex:
+            for s0 in range(0, used, nthr):
+                batch = range(s0, min(s0 + nthr, used))
+                for s, f in zip(batch, ex.map(lambda s: cases.forcing_step(
+                        cols, (julian0 + s * a.dt / 86400.0) % yearlen, yearlen, s, seed=seed),
+                        batch)):
+                    F[s].copy_(torch.from_numpy(f))
     else:
         # two forcing buffers: step k writes buffer k % 2 on each range's stream
         # right before that range's launch (stream order makes reuse safe)
@@ -432,7 +483,11 @@ def main():
         ranges.step(f, cases.CASE_NML_ZSOIL, a.dt, jul, yearlen, d,
                     L.DIAG_OUT_LEVEL if d is not None else L.DIAG_NONE, events=ev, pre=pre)
         sched.finish(k, producers=ranges.producers)
+        if d is not None:
+            last_out[:] = [d, k]
         return d is not None
+
+    last_out = [None, None]  # the block the last output step wrote, and that step
 
     for k in range(a.warmup):
         step(k)
@@ -463,6 +518,10 @@ def main():
         t = torch.tensor([elapsed, kern_ms, step_ms], dtype=torch.float64, device=dev)
         dist.all_reduce(t, op=dist.ReduceOp.MAX)
         elapsed, kern_ms, step_ms = float(t[0]), float(t[1]), float(t[2])
+
+    if a.dump_outputs and rank == 0:
+        d, k = last_out
+        dump_outputs(a.dump_outputs, cs, d if k is not None and k >= a.warmup else None)
 
     if rank == 0:
         colsteps = world * n * a.steps

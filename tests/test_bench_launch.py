@@ -99,6 +99,33 @@ def test_bench_two_ranks_on_the_gpu():
     assert ln["config"]["backend"] == "gloo"
 
 
+@pytest.mark.gpu
+def test_bench_plain_run_dumps_its_outputs(tmp_path):
+    """A plain `bench.py --gpus 1` run times exactly --steps steps, leaves the
+    CPU baseline to --full, and with --dump-outputs writes what the last timed
+    step left (state, ISNOW, status, the last output step's 16 diagnostics) as
+    float32 .npy files of the run's columns."""
+    import numpy as np
+    n = 8192
+    rc, lines, err = run(["--gpus", "1", "--ncol", str(n), "--steps", "3", "--warmup", "1",
+                          "--out-every", "2", "--period", "4", "--dump-outputs", str(tmp_path)],
+                         timeout=240)
+    assert rc == 0, err[-3000:]
+    assert len(lines) == 1, lines
+    ln = lines[0]
+    assert ln["steps"] == 3 and ln["warmup"] == 1 and ln["cpu_baseline"] is None
+    assert ln["ms_per_step"] > 0 and ln["dtype"] == "f32"
+    assert abs(ln["value"] * ln["ms_per_step"] * 1e-3 - n) < 1e-6 * n
+    got = {p.name: np.load(p) for p in tmp_path.glob("*.npy")}
+    shapes = {"state.npy": (56, n), "diag.npy": (16, n), "isnow.npy": (n,), "status.npy": (n,),
+              "columns.npy": (n,)}
+    assert {k: v.shape for k, v in got.items()} == shapes
+    assert all(v.dtype in (np.float32, np.float64) for v in got.values())
+    assert got["state.npy"].dtype == np.float32 and np.isfinite(got["diag.npy"]).all()
+    assert (got["columns.npy"] == np.arange(n)).all() and (got["status.npy"] == 0).all()
+    assert set(np.unique(got["isnow.npy"])) <= {0.0, -1.0, -2.0, -3.0}
+
+
 @pytest.mark.parametrize("how", ["SIGTERM", "SIGKILL"])
 def test_launcher_death_takes_the_ranks_down(tmp_path, how):
     """The ranks run in their own sessions; if the launcher is stopped (a

@@ -12,7 +12,8 @@ from noahmp_amd import params as P
 
 TAGS = [("STAS", "USGS"), ("STAS-RUC", "USGS"), ("STAS", "MODIFIED_IGBP_MODIS_NOAH"),
         ("STAS-RUC", "MODIFIED_IGBP_MODIS_NOAH")]
-REF_TBL = "/root/reference/tbl"
+# the reference's three table files, stored with the fixtures
+REF_TBL = os.path.join(os.path.dirname(os.path.abspath(__file__)), "golden", "tbl")
 
 
 def _assert_same(got: dict, exp: dict):
@@ -31,8 +32,6 @@ def test_builtin_params_match_reference_reader(soil, veg):
 
 @pytest.mark.parametrize("soil,veg", TAGS)
 def test_native_reader_on_reference_tables(engine_lib, soil, veg):
-    if not os.path.isdir(REF_TBL):
-        pytest.skip("reference tables absent (GPU box)")
     _assert_same(P.Params.from_tbl(REF_TBL, soil, veg).as_dict(), load_params(veg, soil))
 
 

@@ -14,7 +14,7 @@ rc=$?; echo "pytest -m gpu rc=$rc"; tail -5 "$OUT/pytest_gpu.log"; ok $rc || exi
 timeout -k 10 240 python -c "import __graft_entry__ as g; g.smoke()" > "$OUT/smoke.log" 2>&1
 rc=$?; echo "smoke rc=$rc"; tail -3 "$OUT/smoke.log"; [ $rc -eq 0 ] || exit $rc
 
-timeout -k 10 ${T_BENCH:-400} python bench.py ${BENCH_ARGS:-} > "$OUT/bench.log" 2>&1
+timeout -k 10 ${T_BENCH:-400} python bench.py --full ${BENCH_ARGS:-} > "$OUT/bench.log" 2>&1
 rc=$?; echo "bench rc=$rc"; tail -3 "$OUT/bench.log"; [ $rc -eq 0 ] || exit $rc
 
 if [ "${PROF:-1}" = 1 ]; then
