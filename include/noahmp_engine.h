@@ -24,6 +24,9 @@
  *   nmp_forcing_from_ldasin_geo, variables the namelist's input files carry (run/case.nml:6-7)
  *   nmp_ldasin_ingest,
  *   nmp_ldasout_grid         (and the LDASOUT file's grids from the step's diagnostics)
+ * nmp_accumulate,             interval totals / means of the output fluxes and the water
+ *   nmp_water_storage,        budget's closure: BEG_WB / END_WB / ERRWAT, which the reference
+ *   nmp_accum_finish          forms and drops             core/module_noahmp_func.f90:339-344, 723-731
  * nmp_frh2o, nmp_frh2o_host   frh2o (public routine)        core/module_noahmp_func.f90:4494-4598
  * nmp_calhum, nmp_calhum_host calhum (public by default)     core/module_noahmp_func.f90:3958-3984
  * nmp_state_from_aos          layout bridge from noahmp_state_t records
@@ -180,6 +183,25 @@ enum {
   NMP_O_FSA = 0, NMP_O_FSR, NMP_O_FIRA, NMP_O_FSH, NMP_O_SSOIL, NMP_O_FCEV, NMP_O_FGEV,
   NMP_O_FCTR, NMP_O_ECAN, NMP_O_ETRAN, NMP_O_EDIR, NMP_O_TRAD, NMP_O_RUNSRF, NMP_O_RUNSUB,
   NMP_O_T2M, NMP_O_ALBEDO, NMP_NDIAG_OUT = 16
+};
+
+/* Accumulators of an output interval (nmp_accumulate), always double: rows
+ * 0..15 mirror NMP_O_* (flux x seconds), row 16 is the precipitation. */
+enum {
+  NMP_ACC_FSA = 0, NMP_ACC_FSR, NMP_ACC_FIRA, NMP_ACC_FSH, NMP_ACC_SSOIL, NMP_ACC_FCEV,
+  NMP_ACC_FGEV, NMP_ACC_FCTR, NMP_ACC_ECAN, NMP_ACC_ETRAN, NMP_ACC_EDIR, NMP_ACC_TRAD,
+  NMP_ACC_RUNSRF, NMP_ACC_RUNSUB, NMP_ACC_T2M, NMP_ACC_ALBEDO, NMP_ACC_PRCP, NMP_NACC = 17
+};
+
+/* An interval's accumulated output (nmp_accum_finish), engine precision: 11
+ * time means (LDASOUT <F>_MEAN), 6 totals in mm (the HRLDAS ACC* fields), the
+ * change of the column's water storage (mm) and the water budget's residual
+ * (mm): DSTOR - (ACCPRCP - ACCECAN - ACCETRAN - ACCEDIR - SFCRNOFF - UGDRNOFF). */
+enum {
+  NMP_B_FSA_MEAN = 0, NMP_B_FSR_MEAN, NMP_B_FIRA_MEAN, NMP_B_FSH_MEAN, NMP_B_SSOIL_MEAN,
+  NMP_B_FCEV_MEAN, NMP_B_FGEV_MEAN, NMP_B_FCTR_MEAN, NMP_B_TRAD_MEAN, NMP_B_T2M_MEAN,
+  NMP_B_ALBEDO_MEAN, NMP_B_ACCPRCP, NMP_B_ACCECAN, NMP_B_ACCETRAN, NMP_B_ACCEDIR,
+  NMP_B_SFCRNOFF, NMP_B_UGDRNOFF, NMP_B_DSTOR, NMP_B_WBRES, NMP_NBUDGET = 19
 };
 
 /* diag_level for nmp_step */
@@ -367,6 +389,35 @@ int nmp_ldasin_ingest(nmp_engine* eng, int64_t ncol, int64_t ld, int64_t npts,
 int nmp_ldasout_grid(nmp_engine* eng, int64_t ncol, int64_t ld, int64_t npts, int nfield,
                      const void* diag, const int32_t* point, double fill, void* grid_be,
                      void* stream);
+
+/* Accumulated output over an output interval (no reference counterpart: the
+ * reference forms the column water storage and the step's residual ERRWAT,
+ * core/module_noahmp_func.f90:339-344 and :723-731, and drops them).  Device
+ * pointers, SoA with leading dimension ld, possibly offset by a range's first
+ * column like nmp_step's; each call only enqueues one kernel on `stream`.
+ *  - nmp_accumulate: after a step at NMP_DIAG_OUT, acc[f] = acc[f] +
+ *    (double)v * (double)dt for the 16 NMP_O_* rows of `diag` (engine
+ *    precision) and row NMP_A_PRCP of the step's `forcing` block; acc is
+ *    NMP_NACC x ld double for both precisions (NMP_ACC_*), zeroed by the
+ *    caller before the first interval.
+ *  - nmp_water_storage: storage[c] (engine precision) = the reference's
+ *    BEG_WB / END_WB of the column's state, in its operation order:
+ *    ((CANLIQ + CANICE) + SNEQV) + WA, then + (SMC(IZ) * DZSNSO(IZ)) * 1000
+ *    for soil layers 1..4 (DZSNSO from ZSNSO and ISNOW, func.f90:322-328);
+ *    0 where IST != 1 (static_i row NMP_I_IST).
+ *  - nmp_accum_finish: the interval's NMP_B_* block `out` (NMP_NBUDGET x ld,
+ *    engine precision T): means (T)(acc / span_s), totals (T)acc,
+ *    DSTOR = (T)d with d = (double)stor_end - (double)stor_beg, and
+ *    WBRES = (T)(d - (((((P - ECAN) - ETRAN) - EDIR) - RUNSRF) - RUNSUB)) from
+ *    the double totals.  Then every acc entry of the column is set to +0.0 and
+ *    stor_end is copied to stor_beg: the next interval starts with no further
+ *    call.  span_s (seconds accumulated) <= 0 is NMP_E_ARG. */
+int nmp_accumulate(nmp_engine* eng, int64_t ncol, int64_t ld, float dt, const void* diag,
+                   const void* forcing, double* acc, void* stream);
+int nmp_water_storage(nmp_engine* eng, int64_t ncol, int64_t ld, const void* state,
+                      const int32_t* isnow, const int32_t* static_i, void* storage, void* stream);
+int nmp_accum_finish(nmp_engine* eng, int64_t ncol, int64_t ld, double span_s, double* acc,
+                     const void* stor_end, void* stor_beg, void* out, void* stream);
 
 int nmp_run(nmp_engine* eng, int64_t ncol, int64_t ld, const float zsoil[4], float dt,
             float julian0, int32_t yearlen, int32_t nsteps, void* state, int32_t* isnow,

@@ -422,6 +422,43 @@ int nmp_ldasout_grid(nmp_engine* eng, int64_t ncol, int64_t ld, int64_t npts, in
              : NMP_E_DEVICE;
 }
 
+int nmp_accumulate(nmp_engine* eng, int64_t ncol, int64_t ld, float dt, const void* diag,
+                   const void* forcing, double* acc, void* stream) {
+  if (!eng || ncol < 0 || ld < ncol || ld >= kMaxColumns) return NMP_E_ARG;
+  if (ncol == 0) return NMP_OK;
+  if (!diag || !forcing || !acc) return NMP_E_ARG;
+  if (ensure_device(eng->device) != NMP_OK) return NMP_E_DEVICE;
+  return nmp::launch_accumulate(eng->precision, ncol, ld, dt, diag, forcing, acc,
+                                static_cast<hipStream_t>(stream)) == hipSuccess
+             ? NMP_OK
+             : NMP_E_DEVICE;
+}
+
+int nmp_water_storage(nmp_engine* eng, int64_t ncol, int64_t ld, const void* state,
+                      const int32_t* isnow, const int32_t* static_i, void* storage, void* stream) {
+  if (!eng || ncol < 0 || ld < ncol || ld >= kMaxColumns) return NMP_E_ARG;
+  if (ncol == 0) return NMP_OK;
+  if (!state || !isnow || !static_i || !storage) return NMP_E_ARG;
+  if (ensure_device(eng->device) != NMP_OK) return NMP_E_DEVICE;
+  return nmp::launch_water_storage(eng->precision, ncol, ld, state, isnow, static_i, storage,
+                                   static_cast<hipStream_t>(stream)) == hipSuccess
+             ? NMP_OK
+             : NMP_E_DEVICE;
+}
+
+int nmp_accum_finish(nmp_engine* eng, int64_t ncol, int64_t ld, double span_s, double* acc,
+                     const void* stor_end, void* stor_beg, void* out, void* stream) {
+  // !(span_s > 0) also refuses NaN
+  if (!eng || ncol < 0 || ld < ncol || ld >= kMaxColumns || !(span_s > 0.0)) return NMP_E_ARG;
+  if (ncol == 0) return NMP_OK;
+  if (!acc || !stor_end || !stor_beg || !out) return NMP_E_ARG;
+  if (ensure_device(eng->device) != NMP_OK) return NMP_E_DEVICE;
+  return nmp::launch_accum_finish(eng->precision, ncol, ld, span_s, acc, stor_end, stor_beg, out,
+                                  static_cast<hipStream_t>(stream)) == hipSuccess
+             ? NMP_OK
+             : NMP_E_DEVICE;
+}
+
 int nmp_forcing_from_ldasin_geo(nmp_engine* eng, int64_t ncol, int64_t ld, const float* ldasin,
                                 const double* geo, double sin_decl, double cos_decl, double ha0,
                                 void* forcing, void* stream) {

@@ -74,6 +74,18 @@ hipError_t launch_ldasout_grid(int precision, int64_t ncol, int64_t ld, int64_t 
                                const void* diag, const int32_t* point, double fill, void* grid_be,
                                hipStream_t stream);
 
+// csrc/accum.hip: accumulated output over an output interval -- the step's
+// fluxes x dt into the double accumulators, the column water storage, and the
+// interval's means / totals / budget residual (which also starts the next one)
+hipError_t launch_accumulate(int precision, int64_t ncol, int64_t ld, float dt, const void* diag,
+                             const void* forcing, double* acc, hipStream_t stream);
+hipError_t launch_water_storage(int precision, int64_t ncol, int64_t ld, const void* state,
+                                const int32_t* isnow, const int32_t* static_i, void* storage,
+                                hipStream_t stream);
+hipError_t launch_accum_finish(int precision, int64_t ncol, int64_t ld, double span_s, double* acc,
+                               const void* stor_end, void* stor_beg, void* out,
+                               hipStream_t stream);
+
 // csrc/routines.hip: the reference's public routines frh2o / calhum over n
 // elements (device pointers, engine precision; math 0 = the fp32 "ref" policy)
 hipError_t launch_frh2o(int precision, int math, const DevParams* P, int64_t n,

@@ -15,6 +15,9 @@ offline/noahmp_config.py has no time loop, forcing reader or writer, SURVEY
 * output steps (Config.output_frequency) write the 16 surface fluxes as
   ``<outdir>/<YYYYMMDDHH>.LDASOUT_DOMAIN1`` (netCDF-3 on the grid, ncio.py)
   when the columns come from a grid, else ``<outdir>/<YYYYMMDDHH>.LDASOUT.npz``;
+  with ``accumulate=True`` each file also carries the interval's accumulated
+  output (layout.BUDGET: means, totals and the water budget's closure, added up
+  on the device after every step: nmp_accumulate / nmp_accum_finish);
 * restart steps (Config.restart_frequency, calendar months allowed) write the
   complete SoA state (``RESTART.<YYYYMMDDHH>_DOMAIN1.nc`` on a grid, else
   ``.npz``), which `load_restart` reads back -- the state SoA *is* the restart
@@ -192,7 +195,7 @@ class OfflineDriver:
                  params: Params | None = None, forcing=None, precision: int = 4,
                  math: str = "ref", zsoil=cases.CASE_NML_ZSOIL, write: bool = True,
                  streams: int = 2, grid: ncio.Grid | None = None, ldasin_upload: bool = True,
-                 cosz: str = "device", ingest: bool = True):
+                 cosz: str = "device", ingest: bool = True, accumulate: bool = False):
         """cols: this rank's columns (all of them on a single rank); under an
         initialised process group they must be the rank's shard_range block of
         the global column set.  ldasin_upload: with a provider that has
@@ -204,7 +207,15 @@ class OfflineDriver:
         ingest: with cosz="device", upload each file's bytes as it stores them
         (its big-endian grids, ncio.LdasinForcing.grid_raw) and select, order
         and byte-swap this rank's columns on the device (nmp_ldasin_ingest)
-        instead of on the host (ncio.LdasinForcing.block)."""
+        instead of on the host (ncio.LdasinForcing.block).
+        accumulate: also write each output interval's accumulated output
+        (layout.BUDGET: time means of the energy fluxes, totals of the water
+        fluxes, the water storage's change and the budget's residual) after
+        the output step's 16 fluxes -- 35 fields per file.  Every step then
+        writes its fluxes (DIAG_OUT_LEVEL) and nmp_accumulate adds them up on
+        the range's stream right after the step; output steps also close the
+        interval there (nmp_water_storage, nmp_accum_finish).  Off (the
+        default), every code path and output byte is as without it."""
         if cosz not in ("device", "host"):
             raise ValueError(f"cosz must be 'device' or 'host', not {cosz!r}")
         self.cfg = cfg
@@ -237,7 +248,23 @@ class OfflineDriver:
         self.t = cfg.begdatetime
         self.step_index = 0
         self.write = write
-        self.diag = torch.zeros((L.NDIAG_OUT, self.cs.ncol), dtype=self.dtype, device=self.dev)
+        self.accumulate = bool(accumulate)
+        self.out_names = L.DIAG_OUT_ACC if self.accumulate else L.DIAG_OUT
+        nout = len(self.out_names)
+        self.diag = torch.zeros((nout, self.cs.ncol), dtype=self.dtype, device=self.dev)
+        if self.accumulate:
+            n = self.cs.ncol
+            self.acc = torch.zeros((L.NACC, n), dtype=torch.float64, device=self.dev)
+            # the fluxes of the steps between output steps (every step writes them)
+            self.acc_diag = torch.zeros((L.NDIAG_OUT, n), dtype=self.dtype, device=self.dev)
+            self.stor_beg = torch.zeros(n, dtype=self.dtype, device=self.dev)
+            self.stor_end = torch.zeros(n, dtype=self.dtype, device=self.dev)
+            self._start_interval()
+            if grid is not None:
+                # a grid whose 35 fields pass the classic format's offsets fails
+                # here, not on a writer thread after the first interval
+                ncio.ldasout_header(grid, "f4" if self.dtype == torch.float32 else "f8",
+                                    cfg.begdatetime, self.out_names)
         self.upload = ForcingUpload(self.cs.ncol, self.dtype, self.dev)
         self.raw_upload = None
         if ldasin_upload and hasattr(self.forcing, "raw") and self.dev_forcing is None:
@@ -263,7 +290,7 @@ class OfflineDriver:
         self.phase_s = defaultdict(float)
         self.gather = None
         if dist.is_initialized():
-            self.gather = shard.DiagGather(L.NDIAG_OUT, total, self.dtype, self.dev, dst=0)
+            self.gather = shard.DiagGather(nout, total, self.dtype, self.dev, dst=0)
             if self.gather.n_local != self.cs.ncol:
                 raise ValueError(f"rank {dist.get_rank()} holds {self.cs.ncol} columns, its "
                                  f"shard_range block of {total} has {self.gather.n_local}")
@@ -276,10 +303,10 @@ class OfflineDriver:
             # the whole set's fluxes costs tens of ms inside the time loop (the
             # file's grids in its byte order when the run has a grid)
             if grid is not None:
-                self._writer_init((L.NDIAG_OUT, grid.shape[0] * grid.shape[1]),
+                self._writer_init((nout, grid.shape[0] * grid.shape[1]),
                                   torch.int32 if self.dtype == torch.float32 else torch.int64)
             else:
-                self._writer_init((L.NDIAG_OUT, total))
+                self._writer_init((nout, total))
         self._out_point = None
 
     @classmethod
@@ -312,6 +339,10 @@ class OfflineDriver:
         drv = cls(cfg, cols, device, P, forcing, grid=grid, **kw)
         drv.t, drv.step_index = t0, step
         drv.perm, drv.cols_index = perm, idx
+        if drv.accumulate:
+            a = ncio.read_accum(init or cfg.initfile, grid)
+            if a is not None:  # a restart written part way through an interval
+                drv._start_interval(a[0][:, idx], a[1][idx], a[2])
         return drv
 
     def to_grid_order(self, a: np.ndarray) -> np.ndarray:
@@ -323,21 +354,63 @@ class OfflineDriver:
         out[..., perm] = a
         return out
 
+    # ---- accumulated output -----------------------------------------------------
+    def _start_interval(self, acc=None, stor_beg=None, steps: int = 0):
+        """The accumulation state of an output interval: fresh (zero
+        accumulators, the beginning storage formed from the state as it is,
+        nmp_water_storage) or, part way through one, what a restart carried.
+        On the current stream, which the ranges' next step waits for."""
+        self.acc_steps = int(steps)
+        if acc is None:
+            self.acc.zero_()
+            self.engine.water_storage(self.cs, self.stor_beg)
+            return
+        self.acc.copy_(torch.as_tensor(np.ascontiguousarray(acc, np.float64), device=self.dev))
+        self.stor_beg.copy_(torch.as_tensor(np.ascontiguousarray(stor_beg), device=self.dev))
+
+    def _accum_post(self, fluxes, forcing, budget, span_s):
+        """StreamShards.step's `post` of an accumulating step: add the step's
+        fluxes and precipitation to the accumulators; at an output step
+        (budget: the output block's rows 16..34) also close the interval."""
+        def post(st, rng):
+            self.engine.accumulate(fluxes, forcing, self.acc, self.dt, stream=st, cols=rng)
+            if budget is not None:
+                self.engine.water_storage(self.cs, self.stor_end, stream=st, cols=rng)
+                self.engine.accum_finish(self.acc, self.stor_end, self.stor_beg, budget, span_s,
+                                         stream=st, cols=rng)
+        return post
+
     # ---- restart -----------------------------------------------------------------
     def save_restart(self, path: str):
+        """With accumulation on, the interval so far travels with the state:
+        the accumulators, the interval's beginning storage and the number of
+        steps accumulated (npz: arrays acc, stor_beg, acc_steps; netCDF:
+        ncio.write_state's accum)."""
         self.ranges.join()
+        accum = None
+        if self.accumulate:
+            accum = (self.acc.cpu().numpy(), self.stor_beg.cpu().numpy(), self.acc_steps)
         if path.endswith(".nc"):
+            if accum is not None:
+                accum = (self.to_grid_order(accum[0]), self.to_grid_order(accum[1]), accum[2])
             ncio.write_state(path, self.grid, self.to_grid_order(self.cs.state.cpu().numpy()),
                              self.to_grid_order(self.cs.isnow.cpu().numpy()), self.t,
-                             self.step_index)
+                             self.step_index, accum=accum)
             return
-        np.savez(path, time=np.array(self.t.isoformat()), step=np.int64(self.step_index),
+        extra = {} if accum is None else dict(acc=accum[0], stor_beg=accum[1],
+                                              acc_steps=np.int64(accum[2]))
+        np.savez(path, **extra, time=np.array(self.t.isoformat()), step=np.int64(self.step_index),
                  state=self.cs.state.cpu().numpy(), isnow=self.cs.isnow.cpu().numpy(),
                  static_f=self.cs.static_f.cpu().numpy(), static_i=self.cs.static_i.cpu().numpy(),
                  status=self.cs.status.cpu().numpy(), zsoil=np.asarray(self.zsoil, np.float32),
                  layout=np.array(",".join(n for n, _ in L.STATE_FIELDS)))
 
     def load_restart(self, path: str):
+        """With accumulation on, a restart that carries an interval's
+        accumulation state (save_restart of an accumulating run) resumes that
+        interval; one without it starts a fresh interval at this point: zero
+        accumulators and the beginning storage formed from the loaded state,
+        so the next output's totals and means cover the steps from here."""
         self.ranges.join()  # no range may still be stepping the state being replaced
         # the resident LDASIN blocks and the read-ahead belong to the old time:
         # a block kept across a jump could sit in a slot the next upload reuses
@@ -352,6 +425,9 @@ class OfflineDriver:
             self.cs.state.copy_(torch.as_tensor(np.ascontiguousarray(st[:, idx]),
                                                 device=self.dev))
             self.cs.isnow.copy_(torch.as_tensor(np.ascontiguousarray(isn[idx]), device=self.dev))
+            if self.accumulate:
+                a = ncio.read_accum(path, self.grid)
+                self._start_interval(*(() if a is None else (a[0][:, idx], a[1][idx], a[2])))
             return
         with np.load(path, allow_pickle=False) as z:
             assert str(z["layout"]) == ",".join(n for n, _ in L.STATE_FIELDS), "state layout"
@@ -360,6 +436,9 @@ class OfflineDriver:
             self.t = datetime.datetime.fromisoformat(str(z["time"]))
             self.step_index = int(z["step"])
             self.zsoil = [float(v) for v in z["zsoil"]]
+            if self.accumulate:
+                self._start_interval(*((z["acc"], z["stor_beg"], int(z["acc_steps"]))
+                                       if "acc" in z.files else ()))
 
     # ---- time loop -----------------------------------------------------------------
     # the interpreter's thread switch interval while the loop runs: the file
@@ -448,9 +527,20 @@ class OfflineDriver:
             if out and self._diag_free is not None:
                 # the output stream's last read of the diagnostics buffer
                 after = (after if isinstance(after, tuple) else (after,)) + (self._diag_free,)
+            dstep, level, post = None, L.DIAG_NONE, None
+            if out:
+                dstep, level = diag, L.DIAG_OUT_LEVEL
+            if self.accumulate:
+                # every step writes its fluxes: the output step's into rows
+                # 0..15 of the output block, the others' into a scratch block
+                dstep, level = diag[:L.NDIAG_OUT] if out else self.acc_diag, L.DIAG_OUT_LEVEL
+                self.acc_steps += 1
+                post = self._accum_post(dstep, f, diag[L.NDIAG_OUT:] if out else None,
+                                        self.acc_steps * self.dt)
+                if out:
+                    self.acc_steps = 0
             self.ranges.step(f, self.zsoil, self.dt, timeman.julian(t0), timeman.yearlen(t0.year),
-                             diag if out else None, L.DIAG_OUT_LEVEL if out else L.DIAG_NONE,
-                             after=after, pre=pre)
+                             dstep, level, after=after, pre=pre, post=post)
             if upload is not None:
                 upload.consumed_by(self.ranges.producers, slot)
             if self.geo is not None and self.ingest is not None:
@@ -545,7 +635,8 @@ class OfflineDriver:
 
     # ---- output -----------------------------------------------------------------
     def _write_output(self, d: torch.Tensor, path: str, t1: datetime.datetime, stream=None):
-        """One output step's (16, n) fluxes, written on a background thread:
+        """One output step's (16, n) fluxes (35 fields with accumulation),
+        written on a background thread:
         on `stream` (after the step that produced them) the engine lays them
         on the file's grids in its byte order (nmp_ldasout_grid)
         and they are copied into the next of OUT_BUFFERS pinned host buffers;
@@ -563,7 +654,7 @@ class OfflineDriver:
                 self._out_point = torch.as_tensor(
                     (idx if perm is None else idx[perm]).astype(np.int32), device=self.dev)
                 npts = self.grid.shape[0] * self.grid.shape[1]
-                self._out_dev = torch.empty((L.NDIAG_OUT, npts), device=self.dev,
+                self._out_dev = torch.empty((d.shape[0], npts), device=self.dev,
                                             dtype=torch.int32 if d.dtype == torch.float32
                                             else torch.int64)
             self.engine.ldasout_grid(d, self._out_point, self._out_dev, float(ncio.FILL),
@@ -588,10 +679,11 @@ class OfflineDriver:
             a = h.numpy()
             if self.grid is not None:
                 ncio.write_ldasout_grids(path, self.grid,
-                                         a.view(">f4" if a.itemsize == 4 else ">f8"), t1)
+                                         a.view(">f4" if a.itemsize == 4 else ">f8"), t1,
+                                         self.out_names)
             else:
                 np.savez(path, time=np.array(t1.isoformat()),
-                         fields=np.array(",".join(L.DIAG_OUT)), diag=a)
+                         fields=np.array(",".join(self.out_names)), diag=a)
         self._out_fut[k] = self._writer.submit(job)
         return ev
 

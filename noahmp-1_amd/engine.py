@@ -286,6 +286,75 @@ class Engine:
                                               _ptr(point, 0), float(fill), _ptr(out, 0),
                                               C.c_void_p(s.cuda_stream)), "nmp_ldasout_grid")
 
+    # ---- accumulated output (nmp_accumulate / nmp_water_storage / nmp_accum_finish)
+    def _check_block(self, t: torch.Tensor, shape: tuple, dtype, what: str):
+        """A contiguous field-major block (or per-column vector) on the engine's
+        device: the library is handed raw pointers offset by a column index."""
+        assert tuple(t.shape) == shape and t.dtype == dtype, (what, tuple(t.shape), t.dtype)
+        assert t.is_contiguous(), what
+        assert t.device.type == "cuda" and t.device.index == self.device, (what, t.device)
+
+    @staticmethod
+    def _cols_range(n: int, cols) -> tuple[int, int]:
+        lo, hi = (0, n) if cols is None else (int(cols[0]), int(cols[1]))
+        assert 0 <= lo <= hi <= n
+        return lo, hi
+
+    def accumulate(self, diag: torch.Tensor, forcing: torch.Tensor, acc: torch.Tensor, dt: float,
+                   stream=None, cols: tuple[int, int] | None = None):
+        """nmp_accumulate: acc[f] += diag[f] * dt for the 16 output fluxes a
+        step at DIAG_OUT_LEVEL wrote into `diag` (NDIAG_OUT, n) and acc[PRCP] +=
+        forcing[PRCP] * dt from the step's (NFORCING, n) forcing; acc is
+        (NACC, n) float64 for both precisions (layout.ACC).  cols=(lo, hi)
+        accumulates only those columns, enqueued on `stream`."""
+        n = int(acc.shape[1])
+        lo, hi = self._cols_range(n, cols)
+        self._check_block(diag, (L.NDIAG_OUT, n), self.dtype, "diag")
+        self._check_block(forcing, (L.NFORCING, n), self.dtype, "forcing")
+        self._check_block(acc, (L.NACC, n), torch.float64, "acc")
+        s = stream if stream is not None else torch.cuda.current_stream(self.device)
+        _lib.check(self._lib.nmp_accumulate(self._h, hi - lo, n, float(dt), _ptr(diag, lo),
+                                            _ptr(forcing, lo), _ptr(acc, lo),
+                                            C.c_void_p(s.cuda_stream)), "nmp_accumulate")
+
+    def water_storage(self, cs: ColumnState, storage: torch.Tensor, stream=None,
+                      cols: tuple[int, int] | None = None):
+        """nmp_water_storage: storage[c] (n,) = the column's water storage in
+        mm (canopy, snow, aquifer and soil water: the reference's BEG_WB /
+        END_WB), 0 where IST != 1."""
+        n = cs.ncol
+        lo, hi = self._cols_range(n, cols)
+        self._check_block(cs.state, (L.NSTATE, n), self.dtype, "state")
+        self._check_block(cs.isnow, (n,), torch.int32, "isnow")
+        self._check_block(cs.static_i, (L.NSTATIC_I, n), torch.int32, "static_i")
+        self._check_block(storage, (n,), self.dtype, "storage")
+        s = stream if stream is not None else torch.cuda.current_stream(self.device)
+        _lib.check(self._lib.nmp_water_storage(self._h, hi - lo, n, _ptr(cs.state, lo),
+                                               _ptr(cs.isnow, lo), _ptr(cs.static_i, lo),
+                                               _ptr(storage, lo), C.c_void_p(s.cuda_stream)),
+                   "nmp_water_storage")
+
+    def accum_finish(self, acc: torch.Tensor, stor_end: torch.Tensor, stor_beg: torch.Tensor,
+                     out: torch.Tensor, span_s: float, stream=None,
+                     cols: tuple[int, int] | None = None):
+        """nmp_accum_finish: the interval's (NBUDGET, n) block `out`
+        (layout.BUDGET: means over span_s seconds, totals, storage change
+        stor_end - stor_beg and the water budget's residual) from acc (NACC, n)
+        float64; then acc is zeroed and stor_beg takes stor_end, which starts
+        the next interval."""
+        n = int(acc.shape[1])
+        lo, hi = self._cols_range(n, cols)
+        self._check_block(acc, (L.NACC, n), torch.float64, "acc")
+        self._check_block(stor_end, (n,), self.dtype, "stor_end")
+        self._check_block(stor_beg, (n,), self.dtype, "stor_beg")
+        self._check_block(out, (L.NBUDGET, n), self.dtype, "out")
+        assert stor_end.data_ptr() != stor_beg.data_ptr() or n == 0
+        s = stream if stream is not None else torch.cuda.current_stream(self.device)
+        _lib.check(self._lib.nmp_accum_finish(self._h, hi - lo, n, float(span_s), _ptr(acc, lo),
+                                              _ptr(stor_end, lo), _ptr(stor_beg, lo),
+                                              _ptr(out, lo), C.c_void_p(s.cuda_stream)),
+                   "nmp_accum_finish")
+
     # ---- the reference's other public routines (nmp_frh2o / nmp_calhum) ------
     def frh2o(self, sltyp, tkelv, smc, sh2o, status=None, stream=None):
         """frh2o (func.f90:4494-4598) elementwise.  Device tensors (engine
@@ -439,7 +508,7 @@ class StreamShards:
 
     def step(self, forcing: torch.Tensor, zsoil, dt: float, julian: float, yearlen: int,
              diag: torch.Tensor | None = None, diag_level: int = L.DIAG_NONE, events=None,
-             after="current", pre=None):
+             after="current", pre=None, post=None):
         """One step of every range.  `after`: the stream, or a tuple of streams
         and events, whose pending work (the forcing upload, a previous reader
         of `diag`) each range waits for first -- by default the caller's current stream,
@@ -448,7 +517,10 @@ class StreamShards:
         complete (e.g. after a synchronize).
         events: per-range (start, end) pairs.  pre(stream, (lo, hi)): work
         enqueued on each range's stream before its step (e.g. generating that
-        range's forcing on the device, Engine.forcing_synth)."""
+        range's forcing on the device, Engine.forcing_synth).
+        post(stream, (lo, hi)): work enqueued on each range's stream after its
+        step and before its end event (e.g. Engine.accumulate on the step's
+        diagnostics)."""
         if isinstance(after, str) and after == "current":
             after = torch.cuda.current_stream(self.streams[0].device)
         if after is not None and not isinstance(after, (tuple, list)):
@@ -480,6 +552,8 @@ class StreamShards:
                 self.engine.step(self.cs, forcing, zsoil, dt, julian, yearlen, diag, diag_level,
                                  stream=st, cols=None if len(self.streams) == 1 else rng,
                                  order=self.order, cost=self.cost)
+            if post is not None:
+                post(st, rng)
             if events is not None:
                 events[i][1].record(st)
             if self.stagger and self.nstep == 0:

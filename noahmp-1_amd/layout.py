@@ -34,6 +34,21 @@ DIAG_FULL = [
 ]
 DIAG_OUT = ["FSA", "FSR", "FIRA", "FSH", "SSOIL", "FCEV", "FGEV", "FCTR", "ECAN", "ETRAN", "EDIR",
             "TRAD", "RUNSRF", "RUNSUB", "T2M", "ALBEDO"]
+# accumulators of an output interval (NMP_ACC_*, always float64): the output
+# fluxes x seconds, then the precipitation
+ACC = DIAG_OUT + ["PRCP"]
+# an interval's accumulated output (NMP_B_*) under its LDASOUT variable names:
+# 11 time means, 6 totals (mm), storage change and water-budget residual (mm)
+BUDGET_MEANS = ["FSA", "FSR", "FIRA", "FSH", "SSOIL", "FCEV", "FGEV", "FCTR", "TRAD", "T2M",
+                "ALBEDO"]
+BUDGET_TOTALS = {"ACCPRCP": "PRCP", "ACCECAN": "ECAN", "ACCETRAN": "ETRAN", "ACCEDIR": "EDIR",
+                 "SFCRNOFF": "RUNSRF", "UGDRNOFF": "RUNSUB"}  # LDASOUT name -> accumulator
+BUDGET = [f"{n}_MEAN" for n in BUDGET_MEANS] + list(BUDGET_TOTALS) + ["DSTOR", "WBRES"]
+NACC = len(ACC)
+NBUDGET = len(BUDGET)
+assert NACC == 17 and NBUDGET == 19
+# the LDASOUT fields of an accumulating run: the output step's fluxes, then the interval's
+DIAG_OUT_ACC = DIAG_OUT + BUDGET
 
 # status bits (NMP_ST_*)
 ST_ERRSW, ST_ERRENG, ST_FIRE, ST_HCAN, ST_ZLVL, ST_FLERCH, ST_OPTVEG, ST_STOP = (

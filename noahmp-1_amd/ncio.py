@@ -23,7 +23,10 @@ scipy.io.netcdf_file (no netCDF-4/HDF5 library exists in this image):
   one variable per state field (layer fields get a layer dimension), ISNOW,
   plus the model time -- the state SoA *is* the restart (SURVEY 8f item 2);
 * LDASOUT, one file per output time, ``<YYYYMMDDHH>.LDASOUT_DOMAIN1``: the 16
-  output fluxes on the grid, _FillValue off the land mask.
+  output fluxes on the grid, _FillValue off the land mask; an accumulating run
+  (driver accumulate=True) appends its interval's 19 fields (layout.BUDGET) and
+  stores the interval so far in its restart files (write_state accum,
+  read_accum).
 
 Columns are the grid's land points (LANDMASK == 1) in row-major order.
 """
@@ -186,8 +189,13 @@ def _month_weighted(g12: np.ndarray, when: datetime.datetime) -> np.ndarray:
 
 # ---- state (initialization / restart) ----------------------------------------------
 def write_state(path: str, grid: Grid, state: np.ndarray, isnow: np.ndarray,
-                t: datetime.datetime, step: int = 0):
-    """SoA state (56, n) + ISNOW on the grid; layer fields get a layer dimension."""
+                t: datetime.datetime, step: int = 0, accum=None):
+    """SoA state (56, n) + ISNOW on the grid; layer fields get a layer dimension.
+    accum: (acc (NACC, n) float64, stor_beg (n,), steps) of an accumulating run
+    part way through an output interval (driver.OfflineDriver(accumulate=True)),
+    stored as double variables ACC_<name> (layout.ACC) and STOR_BEG and the
+    global attribute accum_steps; read_accum reads them, read_state ignores
+    them."""
     ny, nx = grid.shape
     f = netcdf_file(path, "w")
     try:
@@ -211,6 +219,16 @@ def write_state(path: str, grid: Grid, state: np.ndarray, isnow: np.ndarray,
                                  for k in range(w)])
         v = f.createVariable("ISNOW", "i4", dims)
         v[:] = grid.scatter(isnow.astype(np.int32), 0)
+        if accum is not None:
+            acc, stor_beg, nacc = accum
+            assert acc.shape == (L.NACC, grid.n) and stor_beg.shape == (grid.n,)
+            f.accum_steps = np.int32(nacc)
+            fill = np.float64(FILL)
+            for name, row in zip(L.ACC, acc):
+                v = f.createVariable(f"ACC_{name}", "f8", dims)
+                v[:] = grid.scatter(row.astype(np.float64), fill)
+            v = f.createVariable("STOR_BEG", "f8", dims)
+            v[:] = grid.scatter(stor_beg.astype(np.float64), fill)
     finally:
         f.close()
 
@@ -233,6 +251,22 @@ def read_state(path: str, grid: Grid, dtype=np.float32):
         isnow = grid.columns(np.array(f.variables["ISNOW"][:])).astype(np.int32)
         mt = f.model_time.decode() if isinstance(f.model_time, bytes) else f.model_time
         return st, isnow, datetime.datetime.fromisoformat(mt), int(f.model_step)
+    finally:
+        f.close()
+
+
+def read_accum(path: str, grid: Grid):
+    """(acc (NACC, n) float64, stor_beg (n,) float64, steps) of a state file
+    write_state stored an accumulating run's interval in, or None when the
+    file carries none (an initialization file, a run without accumulation)."""
+    f = _read(path)
+    try:
+        if "STOR_BEG" not in f.variables or not hasattr(f, "accum_steps"):
+            return None
+        acc = np.stack([grid.columns(np.array(f.variables[f"ACC_{name}"][:], np.float64))
+                        for name in L.ACC])
+        stor = grid.columns(np.array(f.variables["STOR_BEG"][:], np.float64))
+        return acc, stor, int(f.accum_steps)
     finally:
         f.close()
 
@@ -509,24 +543,27 @@ class LdasinForcing:
 
 # ---- LDASOUT ----------------------------------------------------------------------
 def write_ldasout(path: str, grid: Grid, diag: np.ndarray, t: datetime.datetime,
-                  cols: np.ndarray | None = None, pool=None):
+                  cols: np.ndarray | None = None, pool=None, names=L.DIAG_OUT):
     """The 16 output fluxes (NMP_O_*, (16, n)) on the grid.  cols: column j of
     diag is land point cols[j] (an engine order; default: land-point order).
-    pool: an executor that scatters the fields in parallel."""
+    pool: an executor that scatters the fields in parallel.  names: the
+    variables' names, one per row of diag (an accumulating run's 35:
+    layout.DIAG_OUT_ACC)."""
+    assert diag.shape[0] == len(names)
     ny, nx = grid.shape
     kind = "f8" if diag.dtype == np.float64 else "f4"
     idx = np.asarray(grid.index) if cols is None else np.asarray(grid.index)[cols]
     # the fields scattered straight into the file's (big-endian) element type
-    full = np.empty((len(L.DIAG_OUT), ny * nx), np.dtype(kind).newbyteorder(">"))
+    full = np.empty((len(names), ny * nx), np.dtype(kind).newbyteorder(">"))
 
     def one(i):
         full[i].fill(FILL)
         full[i][idx] = diag[i]
     if pool is None:
-        for i in range(len(L.DIAG_OUT)):
+        for i in range(len(names)):
             one(i)
     else:
-        for fut in [pool.submit(one, i) for i in range(len(L.DIAG_OUT))]:
+        for fut in [pool.submit(one, i) for i in range(len(names))]:
             fut.result()
     f = netcdf_file(path, "w")
     try:
@@ -535,7 +572,7 @@ def write_ldasout(path: str, grid: Grid, diag: np.ndarray, t: datetime.datetime,
         f.createDimension("west_east", nx)
         f.valid_time = t.isoformat()
         dims = ("Time", "south_north", "west_east")
-        for i, name in enumerate(L.DIAG_OUT):
+        for i, name in enumerate(names):
             v = f.createVariable(name, kind, dims)
             v._FillValue = np.asarray(FILL, kind)
             v[0] = full[i].reshape(ny, nx)
@@ -548,10 +585,10 @@ def _nc_name(s: str) -> bytes:
     return np.array(len(b), ">i4").tobytes() + b + b"\x00" * (-len(b) % 4)
 
 
-def ldasout_header(grid: Grid, kind: str, t: datetime.datetime) -> bytes:
+def ldasout_header(grid: Grid, kind: str, t: datetime.datetime, names=L.DIAG_OUT) -> bytes:
     """The netCDF-3 classic header write_ldasout's file has (one record of the
-    16 flux variables over (Time, south_north, west_east), the valid_time
-    global attribute, each variable's _FillValue), built from the format's
+    16 flux variables, or of `names`, over (Time, south_north, west_east), the
+    valid_time global attribute, each variable's _FillValue), built from the format's
     layout: magic, numrecs, dimension / attribute / variable lists, each
     variable's type, per-record size and data offset."""
     ny, nx = grid.shape
@@ -565,35 +602,36 @@ def ldasout_header(grid: Grid, kind: str, t: datetime.datetime) -> bytes:
     vt = t.isoformat().encode("latin1")
     h += [i4(12), i4(1), _nc_name("valid_time"), i4(2), i4(len(vt)), vt,
           b"\x00" * (-len(vt) % 4)]               # NC_ATTRIBUTE, NC_CHAR
-    h += [i4(11), i4(len(L.DIAG_OUT))]           # NC_VARIABLE
+    h += [i4(11), i4(len(names))]                # NC_VARIABLE
     vsize = ny * nx * item
     vsize += -vsize % 4
     metas = []
-    for name in L.DIAG_OUT:
+    for name in names:
         metas.append([_nc_name(name), i4(3), i4(0), i4(1), i4(2), i4(12), i4(1),
                       _nc_name("_FillValue"), i4(nc_type), i4(1), fill, i4(nc_type), i4(vsize)])
     size = sum(len(x) for x in h) + sum(sum(len(x) for x in m) + 4 for m in metas)
     if size + len(metas) * vsize > 2**31 - 1:  # CDF-1 offsets are signed 32-bit
-        raise ValueError(f"LDASOUT of {ny} x {nx} {kind} grids exceeds the classic format's "
-                         "2 GiB offsets")
+        raise ValueError(f"LDASOUT of {len(names)} {ny} x {nx} {kind} grids exceeds the classic "
+                         "format's 2 GiB offsets")
     for i, m in enumerate(metas):
         h += m + [i4(size + i * vsize)]         # begin (32-bit offsets, version 1)
     return b"".join(h)
 
 
-def write_ldasout_grids(path: str, grid: Grid, grids_be: np.ndarray, t: datetime.datetime):
-    """An LDASOUT file from the 16 fluxes already on the file's grids in its
-    byte order (nmp_ldasout_grid's output: (16, npts) big-endian fp32 or
+def write_ldasout_grids(path: str, grid: Grid, grids_be: np.ndarray, t: datetime.datetime,
+                        names=L.DIAG_OUT):
+    """An LDASOUT file from the 16 fluxes (or the fields `names`) already on
+    the file's grids in its byte order (nmp_ldasout_grid's output: (16, npts) big-endian fp32 or
     fp64, FILL off the land points): the header and the bytes, one write --
     the same file write_ldasout produces from the columns."""
     kind = {4: "f4", 8: "f8"}[grids_be.dtype.itemsize]
     ny, nx = grid.shape
-    assert grids_be.shape == (len(L.DIAG_OUT), ny * nx) and grids_be.flags.c_contiguous
+    assert grids_be.shape == (len(names), ny * nx) and grids_be.flags.c_contiguous
     with open(path, "wb") as f:
-        f.write(ldasout_header(grid, kind, t))
+        f.write(ldasout_header(grid, kind, t, names))
         f.write(memoryview(grids_be).cast("B"))
 
 
-def read_ldasout(path: str, grid: Grid) -> np.ndarray:
+def read_ldasout(path: str, grid: Grid, names=L.DIAG_OUT) -> np.ndarray:
     raw = read_ldasin(path)
-    return np.stack([grid.columns(raw[name]) for name in L.DIAG_OUT])
+    return np.stack([grid.columns(raw[name]) for name in names])

@@ -2,7 +2,7 @@
 """Offline Noah-MP run on the MI355X engine: counterpart of run/main.py.
 
     python noahmp_offline.py [case.nml] [--ncol N] [--kind casenml|mixed|conus]
-                             [--device D] [--restart FILE]
+                             [--device D] [--restart FILE] [--accumulate]
 
 Reads the namelist like the reference (noahmp_amd.config.Config ==
 offline/noahmp_config.Config) and then does what the reference driver does
@@ -50,20 +50,25 @@ def main(argv=None):
     ap.add_argument("--no-ingest", action="store_true",
                     help="netCDF cases: build each LDASIN block on the host instead of "
                          "uploading the file's bytes for the device to select and order")
+    ap.add_argument("--accumulate", action="store_true",
+                    help="also write each output interval's accumulated output: time means "
+                         "of the energy fluxes, totals of the water fluxes (ACCPRCP, ACCECAN, "
+                         "..., SFCRNOFF, UGDRNOFF) and the water budget's closure (DSTOR, "
+                         "WBRES) -- 35 fields per LDASOUT file instead of 16")
     a = ap.parse_args(argv)
     cfg = config.Config(a.nmlfile)
     P = Params.builtin()
     if os.path.isfile(cfg.constfile):
         drv = driver.OfflineDriver.from_files(cfg, device=a.device, params=P, init=a.restart,
                                               precision=a.precision, cosz=a.cosz,
-                                              ingest=not a.no_ingest)
+                                              ingest=not a.no_ingest, accumulate=a.accumulate)
         a.ncol = drv.cs.ncol
     else:
         cols = cases.make_columns(a.ncol, a.kind, P.as_dict(), seed=0,
                                   julian=timeman.julian(cfg.begdatetime))
         drv = driver.OfflineDriver(cfg, cols, device=a.device, params=P,
                                    forcing="device" if a.device_forcing else None,
-                                   precision=a.precision)
+                                   precision=a.precision, accumulate=a.accumulate)
         if a.restart:
             drv.load_restart(a.restart)
     t0 = time.perf_counter()

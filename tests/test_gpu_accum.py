@@ -1,0 +1,456 @@
+"""Accumulated output on the GPU: nmp_accumulate / nmp_water_storage /
+nmp_accum_finish against numpy restatements written here (not taken from the
+code under test), and the offline driver with accumulate=True against values
+formed in numpy from the reference's own trajectory (traj_casenml fixture),
+bit for bit, through restart files and two ranks.
+
+Bounds: every comparison is on bits.  The one numeric cap, |WBRES| <= 0.01 mm,
+is the issue's sanity condition: the reference data's own residual over the
+eight intervals peaks at 0.0036 mm (formed on the CPU from the fixture), an
+fp32 ulp of the ~5,250 mm storage is 0.0005 mm; the cap only catches a sign or
+unit error shared by kernel and restatement."""
+import glob
+import os
+
+import numpy as np
+import pytest
+import torch
+
+import noahmp_pkg  # noqa: F401  (spawned ranks re-import this module)
+from golden_io import bit_equal, load
+from noahmp_amd import cases, config, driver, layout as L
+from noahmp_amd.engine import ColumnState, Engine
+from noahmp_amd.lib import NmpError
+from noahmp_amd.params import Params
+
+pytestmark = pytest.mark.gpu
+
+NCOL, LD, LO = 300, 333, 37
+# accumulator rows (mirror of the 16 output fluxes, then PRCP) the budget reads
+MEAN_ROWS = [0, 1, 2, 3, 4, 5, 6, 7, 11, 14, 15]  # FSA..FCTR, TRAD, T2M, ALBEDO
+R_ECAN, R_ETRAN, R_EDIR, R_RUNSRF, R_RUNSUB, R_PRCP = 8, 9, 10, 12, 13, 16
+A_PRCP = 8  # forcing row
+
+
+def ibits(a):
+    a = np.ascontiguousarray(a)
+    return a.view({4: np.int32, 8: np.int64}[a.dtype.itemsize])
+
+
+def same_bits(a, b):
+    a, b = np.asarray(a), np.asarray(b)
+    return a.dtype == b.dtype and a.shape == b.shape and np.array_equal(ibits(a), ibits(b))
+
+
+# ---- numpy restatements ------------------------------------------------------------
+def np_accumulate(acc, diag, forcing, dt):
+    """acc (17, n) float64 after one nmp_accumulate: acc + (double)v * (double)dt."""
+    d = np.float64(np.float32(dt))
+    out = acc.copy()
+    out[:16] = acc[:16] + diag.astype(np.float64) * d
+    out[16] = acc[16] + forcing[A_PRCP].astype(np.float64) * d
+    return out
+
+
+def np_storage(state, isnow, static_i):
+    """BEG_WB / END_WB (func.f90:340-343 with DZSNSO of :322-328) in the
+    arrays' own precision and the reference's operation order; 0 off soil."""
+    T = state.dtype.type
+    one = lambda name, k=0: state[L.STATE_OFF[name][0] + k]  # noqa: E731
+    w = ((one("CANLIQ") + one("CANICE")) + one("SNEQV")) + one("WA")
+    for iz in range(1, 5):                       # Fortran soil layer IZ = C index IZ + 2
+        zb = one("ZSNSO", iz + 2)
+        dz = np.where(isnow + 1 == iz, -zb, one("ZSNSO", iz + 1) - zb)
+        w = w + (one("SMC", iz - 1) * dz) * T(1000)
+    assert w.dtype == state.dtype
+    return np.where(static_i[L.STATIC_I.index("IST")] == 1, w, T(0))
+
+
+def np_finish(acc, stor_end, stor_beg, span_s, dtype):
+    """The (19, n) budget block of nmp_accum_finish from acc (17, n) float64."""
+    out = np.empty((19, acc.shape[1]), dtype)
+    for i, r in enumerate(MEAN_ROWS):
+        out[i] = (acc[r] / np.float64(span_s)).astype(dtype)
+    for i, r in enumerate((R_PRCP, R_ECAN, R_ETRAN, R_EDIR, R_RUNSRF, R_RUNSUB)):
+        out[11 + i] = acc[r].astype(dtype)
+    d = stor_end.astype(np.float64) - stor_beg.astype(np.float64)
+    out[17] = d.astype(dtype)
+    flux = ((((acc[R_PRCP] - acc[R_ECAN]) - acc[R_ETRAN]) - acc[R_EDIR]) - acc[R_RUNSRF]) \
+        - acc[R_RUNSUB]
+    out[18] = (d - flux).astype(dtype)
+    return out
+
+
+def _dev(a):
+    return torch.as_tensor(np.ascontiguousarray(a), device="cuda:0")
+
+
+def _engine(precision):
+    return Engine(Params.builtin(), L.CASE_NML_OPTIONS, device=0, precision=precision)
+
+
+def _fluxes(rng, dtype, ld=LD):
+    """Random (16, ld) output fluxes and a (12, ld) forcing block (PRCP >= 0)."""
+    diag = (rng.normal(size=(16, ld)) * 300.0).astype(dtype)
+    diag[8:11] = np.abs(rng.normal(size=(3, ld)) * 3e-5).astype(dtype)    # ECAN ETRAN EDIR
+    diag[12:14] = np.abs(rng.normal(size=(2, ld)) * 1e-5).astype(dtype)   # RUNSRF RUNSUB
+    forcing = rng.normal(size=(12, ld)).astype(dtype)
+    forcing[A_PRCP] = np.where(rng.random(ld) < 0.5, 0.0, rng.random(ld) * 2e-4).astype(dtype)
+    return diag, forcing
+
+
+# ---- 1. accumulate ----------------------------------------------------------------
+# (ld, lo, hi): the odd ld and offset of the other kernel tests (rows start at
+# any alignment), an even ld with an even offset and an odd column count (every
+# row 16-byte aligned, as a driver's ranges are), the even ld with an odd offset
+ACC_SHAPES = [(LD, LO, NCOL), (334, 38, 301), (334, 37, 300)]
+
+
+@pytest.mark.parametrize("ld,lo,hi", ACC_SHAPES)
+@pytest.mark.parametrize("precision", [4, 8])
+def test_accumulate_is_the_sequential_double_sum(engine_lib, precision, ld, lo, hi):
+    eng = _engine(precision)
+    dtype = np.float32 if precision == 4 else np.float64
+    rng = np.random.default_rng(precision)
+    acc0 = rng.normal(size=(17, ld)) * 1e4
+    acc, want = _dev(acc0), acc0.copy()
+    for dt in (900.0, 900.0, 1800.0):
+        diag, forcing = _fluxes(rng, dtype, ld)
+        eng.accumulate(_dev(diag), _dev(forcing), acc, dt, cols=(lo, hi))
+        want[:, lo:hi] = np_accumulate(want, diag, forcing, dt)[:, lo:hi]
+    torch.cuda.synchronize()
+    got = acc.cpu().numpy()
+    assert same_bits(got[:, lo:hi], want[:, lo:hi])
+    # columns before the range and the padding past ncol are not touched
+    assert same_bits(got[:, :lo], acc0[:, :lo]) and same_bits(got[:, hi:], acc0[:, hi:])
+    eng.close()
+
+
+# ---- 2. water storage --------------------------------------------------------------
+def _random_columns(rng, dtype):
+    state = rng.random(size=(L.NSTATE, LD)).astype(dtype)
+    z = -np.cumsum(rng.random(size=(7, LD)) * 0.5 + 0.01, axis=0)
+    state[L.s("ZSNSO")] = z.astype(dtype)
+    state[L.si("SNEQV")] = (rng.random(LD) * 80.0).astype(dtype)
+    state[L.si("WA")] = (4000.0 + rng.random(LD) * 2000.0).astype(dtype)
+    isnow = rng.choice(np.array([0, -1, -2, -3], np.int32), LD).astype(np.int32)
+    static_i = np.ones((L.NSTATIC_I, LD), np.int32)
+    static_i[L.STATIC_I.index("IST")] = rng.choice(np.array([1, 2], np.int32), LD)
+    return state, isnow, static_i
+
+
+def _column_state(state, isnow, static_i):
+    n = isnow.shape[0]
+    return ColumnState(_dev(state), _dev(isnow),
+                       torch.zeros((L.NSTATIC_F, n), dtype=_dev(state).dtype, device="cuda:0"),
+                       _dev(static_i), torch.zeros(n, dtype=torch.int32, device="cuda:0"))
+
+
+@pytest.mark.parametrize("precision", [4, 8])
+def test_water_storage_is_the_reference_expression(engine_lib, precision):
+    eng = _engine(precision)
+    dtype = np.float32 if precision == 4 else np.float64
+    rng = np.random.default_rng(10 + precision)
+    state, isnow, static_i = _random_columns(rng, dtype)
+    ist = static_i[L.STATIC_I.index("IST")]
+    assert set(np.unique(isnow[LO:NCOL])) == {0, -1, -2, -3} and set(np.unique(ist)) == {1, 2}
+    sentinel = rng.normal(size=LD).astype(dtype)
+    stor = _dev(sentinel)
+    eng.water_storage(_column_state(state, isnow, static_i), stor, cols=(LO, NCOL))
+    torch.cuda.synchronize()
+    got, want = stor.cpu().numpy(), np_storage(state, isnow, static_i)
+    assert same_bits(got[LO:NCOL], want[LO:NCOL])
+    assert (ibits(got[LO:NCOL])[ist[LO:NCOL] == 2] == 0).all()       # +0.0 off soil
+    assert same_bits(got[:LO], sentinel[:LO]) and same_bits(got[NCOL:], sentinel[NCOL:])
+    if precision == 4:
+        # the reference trajectory's own columns, at the start and after 12 steps
+        g = load("traj_casenml.npz")
+        for st, isn in ((g["state0"], g["isnow0"]), (g["states"][11], g["isnows"][11])):
+            out = torch.empty(32, device="cuda:0")
+            eng.water_storage(_column_state(st, isn, g["static_i"]), out)
+            want = np_storage(st, isn, g["static_i"])
+            assert same_bits(out.cpu().numpy(), want)
+            assert (want > 1000.0).all()
+    eng.close()
+
+
+# ---- 3. finish ---------------------------------------------------------------------
+@pytest.mark.parametrize("precision", [4, 8])
+def test_accum_finish_closes_and_restarts_the_interval(engine_lib, precision):
+    eng = _engine(precision)
+    dtype = np.float32 if precision == 4 else np.float64
+    rng = np.random.default_rng(20 + precision)
+    acc = torch.zeros((17, LD), dtype=torch.float64, device="cuda:0")
+    want_acc = np.zeros((17, LD))
+    beg0 = (5800.0 + rng.normal(size=LD) * 50.0).astype(dtype)
+    stor_beg, want_beg = _dev(beg0), beg0.copy()
+    sentinel = rng.normal(size=(19, LD)).astype(dtype)
+    for nstep in (3, 5):                       # two intervals: the second starts from the first's end
+        for _ in range(nstep):
+            diag, forcing = _fluxes(rng, dtype)
+            eng.accumulate(_dev(diag), _dev(forcing), acc, 900.0, cols=(LO, NCOL))
+            want_acc[:, LO:NCOL] = np_accumulate(want_acc, diag, forcing, 900.0)[:, LO:NCOL]
+        end = (want_beg + rng.normal(size=LD)).astype(dtype)
+        stor_end, out = _dev(end), _dev(sentinel)
+        span = nstep * 900.0
+        eng.accum_finish(acc, stor_end, stor_beg, out, span, cols=(LO, NCOL))
+        torch.cuda.synchronize()
+        got = out.cpu().numpy()
+        want = np_finish(want_acc, end, want_beg, span, dtype)
+        assert same_bits(got[:, LO:NCOL], want[:, LO:NCOL])
+        assert same_bits(got[:, :LO], sentinel[:, :LO])
+        assert same_bits(got[:, NCOL:], sentinel[:, NCOL:])
+        # every accumulator of the range is +0.0 and the end storage begins the next interval
+        assert (ibits(acc.cpu().numpy()) == 0).all()
+        assert same_bits(stor_end.cpu().numpy(), end)
+        sb = stor_beg.cpu().numpy()
+        assert same_bits(sb[LO:NCOL], end[LO:NCOL])
+        assert same_bits(sb[:LO], beg0[:LO]) and same_bits(sb[NCOL:], beg0[NCOL:])
+        want_acc[:] = 0.0
+        want_beg[LO:NCOL] = end[LO:NCOL]
+    for bad in (0.0, -900.0):
+        with pytest.raises(NmpError) as e:
+            eng.accum_finish(acc, stor_end, stor_beg, out, bad, cols=(LO, NCOL))
+        assert e.value.code == -1
+    eng.close()
+
+
+# ---- 4. driver against the reference trajectory ---------------------------------------
+def _cols(g):
+    return cases.ColumnSet(g["static_f"], g["static_i"], g["state0"], g["isnow0"], *([None] * 7))
+
+
+def _cfg(tmp_path, sub="out"):
+    from test_config import write_case
+    cfg = config.Config(write_case(tmp_path))
+    cfg.outdir = str(tmp_path / sub)
+    return cfg
+
+
+def _npz_files(outdir):
+    return sorted(glob.glob(os.path.join(outdir, "*.LDASOUT.npz")))
+
+
+def _npz_members(path):
+    with np.load(path, allow_pickle=False) as z:
+        return {k: (z[k].dtype.str, z[k].shape, z[k].tobytes()) for k in z.files}
+
+
+@pytest.fixture(scope="module")
+def traj():
+    return load("traj_casenml.npz")
+
+
+@pytest.fixture(scope="module")
+def acc_run(engine_lib, traj, tmp_path_factory):
+    """The uninterrupted accumulating run of the trajectory's 96 steps (npz
+    output, two ranges of 16 columns): its 8 files and final state."""
+    tmp = tmp_path_factory.mktemp("acc_run")
+    cfg = _cfg(tmp)
+    drv = driver.OfflineDriver(cfg, _cols(traj), forcing=lambda step, t: traj["forcing"][step],
+                               accumulate=True)
+    assert [hi - lo for lo, hi in drv.ranges.ranges] == [16, 16]
+    drv.run()
+    assert drv.step_index == 96
+    files = _npz_files(cfg.outdir)
+    assert len(files) == 8
+    res = dict(files=files, state=drv.cs.state.cpu().numpy(), isnow=drv.cs.isnow.cpu().numpy(),
+               diag=[np.load(f)["diag"] for f in files], dt=drv.dt)
+    drv.engine.close()
+    return res
+
+
+@pytest.fixture(scope="module")
+def twin_t2m(engine_lib, traj):
+    """NMP_O_T2M of every step from a plain engine run of the same columns
+    (the reference's argument list has no composite T2M to compare with)."""
+    from noahmp_amd import timeman
+    import datetime
+    g = traj
+    eng = _engine(4)
+    cs = ColumnState.from_host(_cols(g), "cuda:0")
+    diag = torch.zeros((16, 32), device="cuda:0")
+    t, out = datetime.datetime(2000, 1, 1), []
+    for k in range(96):
+        eng.step(cs, _dev(g["forcing"][k]), cases.CASE_NML_ZSOIL, 900.0, timeman.julian(t),
+                 timeman.yearlen(t.year), diag, L.DIAG_OUT_LEVEL)
+        out.append(diag[L.DIAG_OUT.index("T2M")].cpu().numpy().copy())
+        t = t + datetime.timedelta(seconds=900)
+    assert bit_equal(cs.state.cpu().numpy(), g["states"][-1]).all()
+    eng.close()
+    return np.stack(out)
+
+
+def test_driver_budget_equals_reference_trajectory(acc_run, twin_t2m, traj, tmp_path):
+    g = traj
+    assert acc_run["dt"] == 900.0
+    # the run without accumulation: the 16 fluxes of every file are unchanged
+    cfg = _cfg(tmp_path, "plain")
+    plain = driver.OfflineDriver(cfg, _cols(g), forcing=lambda step, t: g["forcing"][step]).run()
+    plain.engine.close()
+    pfiles = _npz_files(cfg.outdir)
+    assert len(pfiles) == 8
+    assert bit_equal(acc_run["state"], g["states"][-1]).all()
+    assert np.array_equal(acc_run["isnow"], g["isnows"][-1])
+    beg = np_storage(g["state0"], g["isnow0"], g["static_i"])
+    worst = 0.0
+    for j, (fa, fp) in enumerate(zip(acc_run["files"], pfiles)):
+        assert os.path.basename(fa) == os.path.basename(fp)
+        with np.load(fa, allow_pickle=False) as z:
+            d, fields = z["diag"], str(z["fields"]).split(",")
+        with np.load(fp, allow_pickle=False) as z:
+            d16 = z["diag"]
+        assert fields == L.DIAG_OUT_ACC and d.shape == (35, 32) and d.dtype == np.float32
+        assert same_bits(d[:16], d16), f"file {j}: the output step's fluxes changed"
+        # the interval's budget from the reference's own data
+        acc = np.zeros((17, 32))
+        for k in range(12 * j, 12 * j + 12):
+            diag = np.stack([twin_t2m[k] if n == "T2M" else g["diags"][k][L.DIAG_FULL.index(n)]
+                             for n in L.DIAG_OUT])
+            acc = np_accumulate(acc, diag, g["forcing"][k], 900.0)
+        k = 12 * j + 11
+        end = np_storage(g["states"][k], g["isnows"][k], g["static_i"])
+        want = np_finish(acc, end, beg, 12 * 900.0, np.float32)
+        for i, name in enumerate(L.BUDGET):
+            print(f"file {j} {name}: max |value| {np.abs(d[16 + i]).max():.6g}")
+            assert same_bits(d[16 + i], want[i]), (j, name)
+        worst = max(worst, float(np.abs(d[34]).max()))
+        assert (np.abs(d[34]) <= 0.01).all(), f"file {j}: |WBRES| up to {np.abs(d[34]).max()} mm"
+        beg = end
+    print(f"largest |WBRES| over the 8 intervals: {worst:.6f} mm")
+
+
+# ---- 5. restart part way through an interval --------------------------------------------
+def test_restart_mid_interval_npz(acc_run, traj, tmp_path):
+    """40 steps (4 into the fourth interval), restart through an npz file into
+    a fresh accumulating driver: the files of the remaining five intervals
+    hold the uninterrupted run's bytes (every member of the npz archive: its
+    name, dtype, shape and data; the zip container itself stamps each member
+    with the wall-clock time of writing, so two runs' archives differ there)."""
+    g = traj
+    ff = lambda step, t: g["forcing"][step]  # noqa: E731
+    a = driver.OfflineDriver(_cfg(tmp_path, "first"), _cols(g), forcing=ff, accumulate=True)
+    a.run(nsteps=40)
+    assert a.acc_steps == 4
+    path = str(tmp_path / "r.npz")
+    a.save_restart(path)
+    a.engine.close()
+    cfg = _cfg(tmp_path, "second")
+    b = driver.OfflineDriver(cfg, _cols(g), forcing=ff, accumulate=True)
+    b.load_restart(path)
+    assert b.step_index == 40 and b.acc_steps == 4
+    b.run()
+    assert bit_equal(b.cs.state.cpu().numpy(), g["states"][-1]).all()
+    b.engine.close()
+    files = _npz_files(cfg.outdir)
+    assert [os.path.basename(f) for f in files] == \
+        [os.path.basename(f) for f in acc_run["files"][3:]]
+    for got, want in zip(files, acc_run["files"][3:]):
+        assert _npz_members(got) == _npz_members(want), got
+    # a restart without the accumulation state starts a fresh interval there
+    plain = driver.OfflineDriver(_cfg(tmp_path, "p"), _cols(g), forcing=ff, write=False)
+    plain.run(nsteps=40)
+    p2 = str(tmp_path / "plain.npz")
+    plain.save_restart(p2)
+    plain.engine.close()
+    assert "acc" not in np.load(p2).files
+    cfg = _cfg(tmp_path, "third")
+    c = driver.OfflineDriver(cfg, _cols(g), forcing=ff, accumulate=True)
+    c.load_restart(p2)
+    assert c.acc_steps == 0
+    c.run(nsteps=8)
+    c.engine.close()
+    with np.load(_npz_files(cfg.outdir)[0], allow_pickle=False) as z:
+        d = z["diag"]
+    acc = np.zeros((17, 32))
+    for k in range(40, 48):
+        diag = np.stack([np.zeros(32, np.float32) if n == "T2M" else
+                         g["diags"][k][L.DIAG_FULL.index(n)] for n in L.DIAG_OUT])
+        acc = np_accumulate(acc, diag, g["forcing"][k], 900.0)
+    want = np_finish(acc, np_storage(g["states"][47], g["isnows"][47], g["static_i"]),
+                     np_storage(g["states"][39], g["isnows"][39], g["static_i"]), 8 * 900.0,
+                     np.float32)
+    for i, name in enumerate(L.BUDGET):
+        if name != "T2M_MEAN":
+            assert same_bits(d[16 + i], want[i]), name
+
+
+def _netcdf_files(outdir):
+    return sorted(glob.glob(os.path.join(outdir, "*.LDASOUT_DOMAIN1")))
+
+
+def test_restart_mid_interval_netcdf(acc_run, traj, tmp_path):
+    """The same through netCDF files (static / init / LDASIN -> LDASOUT with
+    35 variables, a netCDF restart carrying the interval): byte-identical
+    files after the restart, and every budget variable equal to the npz
+    run's in grid order."""
+    from noahmp_amd import ncio
+    from test_gpu_driver import _write_netcdf_case
+    nml, grid = _write_netcdf_case(tmp_path, traj)
+    cfg = config.Config(str(nml))
+    cfg.outdir = str(tmp_path / "full")
+    full = driver.OfflineDriver.from_files(cfg, accumulate=True).run()
+    assert bit_equal(full.to_grid_order(full.cs.state.cpu().numpy()), traj["states"][-1]).all()
+    full.engine.close()
+    want = _netcdf_files(cfg.outdir)
+    assert len(want) == 8
+    for j, fn in enumerate(want):
+        raw = ncio.read_ldasin(fn)
+        assert list(raw) == L.DIAG_OUT_ACC and len(raw) == 35
+        d = ncio.read_ldasout(fn, grid, L.DIAG_OUT_ACC)
+        assert same_bits(d, acc_run["diag"][j]), fn
+    cfg.outdir = str(tmp_path / "first")
+    a = driver.OfflineDriver.from_files(cfg, accumulate=True).run(nsteps=40)
+    path = str(tmp_path / "RESTART.nc")
+    a.save_restart(path)
+    a.engine.close()
+    got = ncio.read_accum(path, grid)
+    assert got is not None and got[2] == 4
+    cfg.outdir = str(tmp_path / "second")
+    b = driver.OfflineDriver.from_files(cfg, init=path, accumulate=True)
+    assert b.step_index == 40 and b.acc_steps == 4
+    b.run()
+    b.engine.close()
+    files = _netcdf_files(cfg.outdir)
+    assert [os.path.basename(f) for f in files] == [os.path.basename(f) for f in want[3:]]
+    for x, y in zip(files, want[3:]):
+        assert open(x, "rb").read() == open(y, "rb").read(), x
+    # a run without accumulation ignores the restart's extra variables
+    cfg.outdir = str(tmp_path / "plain")
+    c = driver.OfflineDriver.from_files(cfg, init=path, write=False).run()
+    assert bit_equal(c.to_grid_order(c.cs.state.cpu().numpy()), traj["states"][-1]).all()
+    c.engine.close()
+
+
+# ---- 6. two ranks -------------------------------------------------------------------
+def _accum_rank(rank, world, port, nml):
+    import torch.distributed as dist
+    os.environ.update(MASTER_ADDR="127.0.0.1", MASTER_PORT=str(port))
+    dist.init_process_group("gloo", rank=rank, world_size=world)
+    drv = driver.OfflineDriver.from_files(config.Config(nml), accumulate=True)
+    assert drv.gather.nfield == 35
+    drv.run()
+    dist.barrier()
+    drv.engine.close()
+    dist.destroy_process_group()
+
+
+def test_two_ranks_write_the_single_rank_files(engine_lib, traj, tmp_path):
+    import socket
+    import torch.multiprocessing as mp
+    from test_gpu_driver import _write_netcdf_case
+    nml, _grid = _write_netcdf_case(tmp_path, traj)
+    cfg = config.Config(str(nml))
+    out_multi = cfg.outdir
+    cfg.outdir = str(tmp_path / "single")
+    one = driver.OfflineDriver.from_files(cfg, accumulate=True).run()
+    one.engine.close()
+    with socket.socket() as s:
+        s.bind(("127.0.0.1", 0))
+        port = s.getsockname()[1]
+    mp.start_processes(_accum_rank, args=(2, port, str(nml)), nprocs=2, start_method="spawn")
+    multi, single = _netcdf_files(out_multi), _netcdf_files(cfg.outdir)
+    assert len(multi) == len(single) == 8
+    for a, b in zip(multi, single):
+        assert os.path.basename(a) == os.path.basename(b)
+        assert open(a, "rb").read() == open(b, "rb").read(), a
