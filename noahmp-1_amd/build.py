@@ -114,7 +114,7 @@ def check_device_asm(asm_files, verbose: bool = True):
 
 def check_kernarg_layout(asm_files):
     """The fp32 step kernels re-read their array bases from the kernel-argument
-    segment at KArgs' byte offset 8 (sflx_kernel.hip kargs_seg, NMP_OFF32=3).
+    segment at KArgs' byte offset 8 (sflx_kernel.hip kargs_seg, the fp32 translation unit).
     Every sflx_step_kernel's code-object metadata must place its second
     argument (KArgs, by value) at offset 8; a build where it does not is
     refused."""

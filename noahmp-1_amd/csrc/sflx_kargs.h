@@ -10,10 +10,6 @@
 #ifndef NMP_BLOCK
 #define NMP_BLOCK 256
 #endif
-// per-lane LDS slots for the LDS-resident layer work arrays (LArr)
-#ifndef NMP_LDS_SLOTS
-#define NMP_LDS_SLOTS 28
-#endif
 
 namespace nmp {
 

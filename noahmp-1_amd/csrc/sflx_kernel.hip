@@ -38,29 +38,12 @@ struct Col {
   // forcing
   T sfctmp, sfcprs, psfc, uu, vv, q2, soldn, lwdn, prcp, cosz, co2air, o2air;
   // prognostic state
-#ifdef NMP_LDS_STATE
-  LArr<T, 7, 0> stc;
-  LArr<T, 7, 7> zsnso;
-  LArr<T, 3, 14> snice;
-  LArr<T, 3, 17> snliq;
-  LArr<T, 4, 20> sh2o;
-  LArr<T, 4, 24> smc;
-#else
   T stc[7], zsnso[7], snice[3], snliq[3], sh2o[4], smc[4];
-#endif
   T tv, tg, tah, eah, fwet, canliq, canice, qsfc, snowh, sneqv, sneqvo, albold, tauss, qsnow;
   T zwt, wa, wt, wslake, lai, sai, lfmass, rtmass, stmass, wood, stblcp, fastcp, cm, ch;
   int isnow;
   // per-step layer work arrays
-#ifdef NMP_LDS_WORK
-  LArr<T, 7, 0> dz;
-  LArr<T, 7, 7> df;
-  LArr<T, 7, 14> hcpct;
-  LArr<T, 7, 21> fact;
-  T ficeold[3], sice[4], btrani[4];
-#else
   T dz[7], ficeold[3], sice[4], btrani[4], df[7], hcpct[7], fact[7];
-#endif
   int imelt[7];
   int status;
 };
@@ -795,63 +778,47 @@ __host__ __device__ constexpr int out_index(int d) {
 }
 
 // Streaming accesses of the column SoA (state, static, forcing, diagnostics):
-// with the nontemporal hint (NMP_NT, default on), so that the once-read /
-// once-written column data does not displace the register-spill lines from
-// the XCD's L2: HBM traffic 903 -> 858 B per column-step, +0.5 % (config #3)
-// and +0.9 % (config #5) (profiles/r02/nt_ab.txt).  NMP_NT=0: plain accesses.
-#ifndef NMP_NT
-#define NMP_NT 1
-#endif
+// with the nontemporal hint, so that the once-read / once-written column data
+// does not displace the register-spill lines from the XCD's L2: HBM traffic
+// 903 -> 858 B per column-step, +0.5 % (config #3) and +0.9 % (config #5)
+// over plain accesses (profiles/r02/nt_ab.txt).
 template <class T>
 DEV T gld(const T* p) {
-  if constexpr (NMP_NT != 0) return __builtin_nontemporal_load(p);
-  else return *p;
+  return __builtin_nontemporal_load(p);
 }
 template <class T>
 DEV void gst(T* p, T v) {
-  if constexpr (NMP_NT != 0) __builtin_nontemporal_store(v, p);
-  else *p = v;
+  __builtin_nontemporal_store(v, p);
 }
 
 // Column addressing.  Every column array is field-major SoA with the
 // launch's stride `ld`; element (field f, column c) of an array is at
-// base + f*ld + c.  The bases are kernel arguments (SGPRs).  With NMP_OFF32
-// the field's address base + f*ld stays uniform (SGPRs) and the lane adds
-// one 32-bit VGPR, the byte offset c*sizeof(E), the same for every field: the
-// SGPR-base + VGPR-offset form of global loads and stores (column indices
-// below 2^29, which the host's argument checks guarantee).  NMP_OFF32=2
-// also recomputes base + f*ld at every access (a few SALU instructions)
-// rather than letting the compiler keep one live 64-bit base per field,
-// which it spilled to VGPR lanes (94 SGPR spills, 700 v_readlane per step).
-// NMP_OFF32=3 also re-reads the array base itself from the kernel-argument
-// segment at each access (a scalar load) instead of holding the eight bases
-// in SGPRs (892 -> 34 v_readlane).  Spilled VGPRs of the fp32 option-set-1
-// kernel: 36 with 64-bit per-lane pointers (NMP_OFF32=0), 29 with 1, 9 with 2,
-// 6 with 3.  Measured (profiles/r05/off32_ab.txt): 1 over 0 config #3 +1.8 %,
-// config #5 +2.9 %; 2 over 1 +0.8 % and +3.3 %; 3 over 2 config #3 +2.1 %
-// but config #5 -0.9 % and config #2 -6.8 % (fp64).  Default: 3 for the fp32
-// translation unit, 2 for the fp64 one.
-#ifndef NMP_OFF32
-#if defined(NMP_TU) && NMP_TU == 4
-#define NMP_OFF32 3
-#else
-#define NMP_OFF32 2
-#endif
-#endif
+// base + f*ld + c.  The bases are kernel arguments (SGPRs).  The field's
+// address base + f*ld stays uniform (SGPRs) and the lane adds one 32-bit VGPR,
+// the byte offset c*sizeof(E), the same for every field: the SGPR-base +
+// VGPR-offset form of global loads and stores (column indices below 2^29,
+// which the host's argument checks guarantee).  base + f*ld is recomputed at
+// every access (a few SALU instructions) rather than letting the compiler keep
+// one live 64-bit base per field, which it spilled to VGPR lanes (94 SGPR
+// spills, 700 v_readlane per step).  The fp32 translation unit also re-reads
+// the array base itself from the kernel-argument segment at each access (a
+// scalar load) instead of holding the eight bases in SGPRs (892 -> 34
+// v_readlane).  Spilled VGPRs of the fp32 option-set-1 kernel: 36 with 64-bit
+// per-lane pointers, 29 with a shared 32-bit offset, 9 with the recomputed
+// field address, 6 with the re-read bases.  Measured
+// (profiles/r05/off32_ab.txt): 32-bit offset over pointers config #3 +1.8 %,
+// config #5 +2.9 %; recomputing +0.8 % and +3.3 %; re-reading config #3 +2.1 %
+// but config #5 -0.9 % and config #2 -6.8 % (fp64), hence for the fp32
+// translation unit only.
 template <class E>
 DEV E* col_at(E* base, int64_t ld, int64_t col, int f) {
-  if constexpr (NMP_OFF32 != 0) {
-#if NMP_OFF32 >= 2
-    // an opaque copy of the stride per access: base + f*ld is formed here,
-    // not shared with (and kept live for) the other accesses to field f
-    __asm__ volatile("" : "+s"(ld));
-#endif
-    return (E*)((char*)(base + f * ld) + (uint32_t)((uint32_t)col * (uint32_t)sizeof(E)));
-  } else
-    return base + (f * ld + col);
+  // an opaque copy of the stride per access: base + f*ld is formed here,
+  // not shared with (and kept live for) the other accesses to field f
+  __asm__ volatile("" : "+s"(ld));
+  return (E*)((char*)(base + f * ld) + (uint32_t)((uint32_t)col * (uint32_t)sizeof(E)));
 }
 
-#if NMP_OFF32 == 3
+#if defined(NMP_TU) && NMP_TU == 4
 // the array bases re-read from the kernel-argument segment at every access
 // (scalar loads) instead of being held in SGPRs: the step kernel's arguments
 // are (const DevParams*, KArgs<T>), KArgs at byte offset 8 (the code object's
@@ -932,25 +899,12 @@ struct Sink {
 // fields before the second read.  (Issuing the
 // copy later, as a prefetch before the flux loops, does not hide its latency:
 // vmcnt counts in order, so the first spill reload after it waits for it.)
-#ifndef NMP_PREFETCH
-#define NMP_PREFETCH 3
-#endif
-// explicit wait for the copy before its first read (tuning A/B only: 0 leaves
-// the wait to the compiler's LDS-DMA alias tracking, as round 2 did)
-#ifndef NMP_LDS_EXPLICIT_WAIT
-#define NMP_LDS_EXPLICIT_WAIT 1
-#endif
 constexpr int kPrefetchFields = NMP_S_SMC + 4;
 static_assert(NMP_S_STC == 0 && NMP_S_ZSNSO == 7 && NMP_S_SNICE == 14 && NMP_S_SNLIQ == 17 &&
                   NMP_S_SH2O == 20 && NMP_S_SMC == 24,
               "prefetch slots are state fields 0..27");
 template <class T, bool R>
-constexpr bool kPrefetch = NMP_PREFETCH != 0 && sizeof(T) == 4 && R;
-// (tuning: bit 0 = entry reads from the copy, bit 1 = the re-read from it)
-template <class T, bool R>
-constexpr bool kPfEntry = kPrefetch<T, R> && (NMP_PREFETCH & 1);
-template <class T, bool R>
-constexpr bool kPfReread = kPrefetch<T, R> && (NMP_PREFETCH & 2);
+constexpr bool kPrefetch = sizeof(T) == 4 && R;
 typedef __attribute__((address_space(3))) float lds_f32;
 DEV lds_f32* lds_pool() {
   __shared__ float pool[kPrefetchFields * NMP_BLOCK];
@@ -967,7 +921,7 @@ DEV void copy_layers_to_lds(const T* st, int64_t ld) {
   for (int f = 0; f < kPrefetchFields; ++f)
     __builtin_amdgcn_global_load_lds((const void*)(st + f * ld),
                                      (__attribute__((address_space(3))) void*)(pool + f * NMP_BLOCK + wbase),
-                                     4, 0, NMP_NT != 0 ? 2 : 0);  // aux bit 1: nt
+                                     4, 0, 2);  // aux bit 1: nt
 }
 
 // Optional per-phase timing (build with -DNMP_PHASE_TIMING; tools only):
@@ -1018,68 +972,6 @@ static __device__ unsigned int nmp_fallback_ctr;
 static __device__ unsigned int nmp_fb_reason[32];
 #endif
 
-
-// Unroll factor of the vege_flux Newton loop (tuning knob, results identical).
-// NMP_VEGE_DIV: the canopy Newton loop divides with DivFast32 where its range
-// proofs hold (fp32 "ref" option-set kernels), IEEE otherwise
-#ifndef NMP_VEGE_DIV
-#define NMP_VEGE_DIV 1
-#endif
-// NMP_BARE_DIV: the same for the bare-ground Newton loop (bare_flux)
-#ifndef NMP_BARE_DIV
-#define NMP_BARE_DIV 1
-#endif
-// NMP_SOIL_DIV: the soil-water sub-steps' divisions by the layer thicknesses
-// (launch-uniform) with DivFast32, a tiny numerator on IEEE division
-#ifndef NMP_SOIL_DIV
-#define NMP_SOIL_DIV 1
-#endif
-// NMP_VD_CHECKED: bit 0 the canopy loop's CTR, TR and DTV, bit 1 the bare
-// loop's DTG also divide with DivFast32, their numerators checked per lane
-// every iteration (vege_domain.h NUM_LO_EXP / NUM_HI_EXP; outside: the lane
-// re-runs its loop with IEEE division).  Both on: config #3 +0.4 to +1.4 %
-// interleaved on two boxes, neither alone measurable
-// (profiles/r06/ab/vd_checked_ab.txt)
-#ifndef NMP_VD_CHECKED
-#define NMP_VD_CHECKED 3
-#endif
-#ifndef NMP_VEGE_UNROLL
-#define NMP_VEGE_UNROLL 1
-#endif
-// NMP_SKIP_2M=0: the 2-m diagnostic chain also on steps without diagnostics (A/B)
-#ifndef NMP_SKIP_2M
-#define NMP_SKIP_2M 1
-#endif
-// Unroll factors of the fixed 5-iteration under-canopy (loop2) and bare_flux
-// Newton loops (tuning knobs, results identical).  bare_flux is unrolled in
-// the fp32 kernels: config #3 +0.8 %, fewer spills (59 -> 52); fp64 and
-// loop2 measured no gain (profiles/r02/unroll_ab.txt).
-#ifndef NMP_LOOP2_UNROLL
-#define NMP_LOOP2_UNROLL 1
-#endif
-#ifndef NMP_BARE_UNROLL
-#define NMP_BARE_UNROLL sizeof(T) == 4 ? 5 : 1
-#endif
-// Late loads of the flux and water phases (fields first read there), issued
-// where they are first needed (NMP_EARLY_LOADS=0) or a phase earlier, so
-// that their memory latency overlaps the phase before (bit 1: water fields
-// after the flux loops; bit 2: flux fields before btran/rsurf).  Values are
-// the same either way: nothing stores these fields before the loads.
-#ifndef NMP_EARLY_LOADS
-#define NMP_EARLY_LOADS 0
-#endif
-#define NMP_FLUX_LOADS()                                                                     \
-  c.tah = out.ls(NMP_S_TAH); c.eah = out.ls(NMP_S_EAH); c.canliq = out.ls(NMP_S_CANLIQ);     \
-  c.canice = out.ls(NMP_S_CANICE); c.qsfc = out.ls(NMP_S_QSFC); c.cm = out.ls(NMP_S_CM);     \
-  c.ch = out.ls(NMP_S_CH); c.tbot = out.lf(NMP_F_TBOT); c.foln = out.lf(NMP_F_FOLN);         \
-  c.co2air = out.la(NMP_A_CO2AIR); c.o2air = out.la(NMP_A_O2AIR)
-#define NMP_WATER_LOADS()                                                                    \
-  const T prcp_w = out.la(NMP_A_PRCP), uu_w = out.la(NMP_A_UU), vv_w = out.la(NMP_A_VV);     \
-  c.zwt = out.ls(NMP_S_ZWT); c.wa = out.ls(NMP_S_WA); c.wt = out.ls(NMP_S_WT);               \
-  c.wslake = out.ls(NMP_S_WSLAKE);                                                           \
-  c.slptyp = out.li(NMP_I_SLOPETYP)
-#define NMP_STR(x) #x
-#define NMP_UNROLL(n) _Pragma(NMP_STR(unroll n))
 
 // Option sets compiled as constants (kernel template parameter OS): with the
 // options known at compile time every `if (o.xxx == k)` of the other values
@@ -1203,7 +1095,7 @@ DEV void sflx_column(const DevParams& P, const KArgs<T>& A, Col<T>& c, const Sin
   T t2mv = 0, q2v = 0, chv = 0, chleaf = 0, chuc = 0, chv2 = 0, rssun = 0, rssha = 0;
   // the diagnostic-only chains (the 2-m MOZ2 -> FH2 -> CHV2/CHB2 -> T2M, Q2;
   // TRAD) only when the step writes diagnostics: nothing else reads them
-  const bool diag_on = !NMP_SKIP_2M || out.level != NMP_DIAG_NONE;
+  const bool diag_on = out.level != NMP_DIAG_NONE;
   T bgap = 0, wgap = 0;
   T ur = rmax(M::sqrt(c.uu * c.uu + c.vv * c.vv), L(1.0));
   T vai = elai + esai;
@@ -1389,10 +1281,6 @@ DEV void sflx_column(const DevParams& P, const KArgs<T>& A, Col<T>& c, const Sin
   else
     emg = (T)P.g.emslake * (L(1.0) - fsno) + L(1.0) * fsno;
   NMP_PHASE(3);
-#if NMP_EARLY_LOADS & 2
-  // the flux phase's fields issued here, their latency under btran/rsurf
-  NMP_FLUX_LOADS();
-#endif
   // soil moisture stress (:1117-1140)
   T btran = L(0.0);
 #pragma unroll
@@ -1447,15 +1335,14 @@ DEV void sflx_column(const DevParams& P, const KArgs<T>& A, Col<T>& c, const Sin
   const T gammag = CPAIR * c.sfcprs / (L(0.622) * latheag);
   const T stc_top = dget(c.stc, kt), dz_top = dget(c.dz, kt);
 
-  // fields first used by the flux phase
-#if !(NMP_EARLY_LOADS & 2)
-  NMP_FLUX_LOADS();
-#endif
+  // fields first used by the flux phase: read here, not a phase earlier
+  // (issuing them before btran/rsurf to overlap their latency measured no
+  // gain, profiles/r05/early_loads_ab.txt)
+  c.tah = out.ls(NMP_S_TAH); c.eah = out.ls(NMP_S_EAH); c.canliq = out.ls(NMP_S_CANLIQ);
+  c.canice = out.ls(NMP_S_CANICE); c.qsfc = out.ls(NMP_S_QSFC); c.cm = out.ls(NMP_S_CM);
+  c.ch = out.ls(NMP_S_CH); c.tbot = out.lf(NMP_F_TBOT); c.foln = out.lf(NMP_F_FOLN);
+  c.co2air = out.la(NMP_A_CO2AIR); c.o2air = out.la(NMP_A_O2AIR);
   NMP_PHASE(4);
-// NMP_DOM_MASK (timing probes only, not exact in general): the checks kept
-#ifndef NMP_DOM_MASK
-#define NMP_DOM_MASK 0xffffffffu
-#endif
 #ifdef NMP_COUNT_FALLBACK
   // (probe builds) which condition sent the lane to an IEEE loop
   unsigned fb_why = 0;
@@ -1466,7 +1353,7 @@ DEV void sflx_column(const DevParams& P, const KArgs<T>& A, Col<T>& c, const Sin
     if (!c_) fb_why |= 1u << (bit);              \
   } while (0)
 #else
-#define NMP_DOM(flag, bit, cond) flag = flag & (((NMP_DOM_MASK >> (bit)) & 1) == 0 || (cond))
+#define NMP_DOM(flag, bit, cond) flag = flag & (bool)(cond)
 #endif
   // ---- vege_flux: func.f90:2465-2964 ----
   T tgv = L(0.0), cmv = L(0.0);
@@ -1526,12 +1413,7 @@ DEV void sflx_column(const DevParams& P, const KArgs<T>& A, Col<T>& c, const Sin
       NMP_DOM(k, 12, in(fveg, NMP_DOM_FVEG_LO, 1.0));
       NMP_DOM(k, 13, in(sqrt_dleaf_uc, NMP_DOM_SDL_LO, NMP_DOM_SDL_HI));
       NMP_DOM(k, 14, in(rsurf, 0.0, NMP_DOM_RSURF_HI));
-#if NMP_VD_CHECKED & 1
       NMP_DOM(k, 15, in(emg, 0.0, 1.0));  // bounds DTV's denominator A
-#endif
-#ifdef NMP_VD_NODOMAIN
-      k = true;  // (timing probe only: not exact in general)
-#endif
       return k;
     };
     // The whole canopy Newton loop (loop1, func.f90:2744-2877) with the
@@ -1541,13 +1423,12 @@ DEV void sflx_column(const DevParams& P, const KArgs<T>& A, Col<T>& c, const Sin
       constexpr bool kFast = !std::is_same<std::decay_t<decltype(d)>, DivRef<T>>::value;
       // CTR, TR and DTV: their numerators are products of several possibly
       // small factors, outside what the range proof bounds statically
-      // (tools/div_proof.py).  IEEE division, or with NMP_VD_CHECKED the
-      // loop's policy and a per-lane window on each numerator (`nwin`).
-#if defined(NMP_VD_ALLFAST) || (NMP_VD_CHECKED & 1)
-      auto& dref = d;  // (NMP_VD_ALLFAST: timing probe only, not exact in general)
-#else
-      const DivRef<T> dref;
-#endif
+      // (tools/div_proof.py).  They too divide with the loop's policy, behind a
+      // per-lane window on each numerator (`nwin`, vege_domain.h NUM_LO_EXP /
+      // NUM_HI_EXP; outside: the lane re-runs its loop with IEEE division).
+      // With the bare loop's DTG, over IEEE division at these sites: config #3
+      // +0.4 to +1.4 % interleaved on two boxes, neither loop alone measurable
+      // (profiles/r06/ab/vd_checked_ab.txt)
       // the per-iteration windows of the range proof (vege_domain.h): TV at
       // the start of every iteration, RAHG after every ragrb, RSSUN/RSSHA after
       // the first iteration; any miss sends the lane through the IEEE loop
@@ -1594,9 +1475,7 @@ DEV void sflx_column(const DevParams& P, const KArgs<T>& A, Col<T>& c, const Sin
         const Recip<T> rrahc = d.rec(rahc);  // RAWC = RAHC: CAH = CAW, H share it
         ragrb<T, R>(d, inv.rhocp, rhcan, dzg, sqrt_dleaf_uc, iter, vaie, hg, c.tah, zpd, z0mg, hcan,
                     z0h, fv, cwp, mpe, fhg, rahg, rb);
-#ifndef NMP_VD_NOWIN
         if constexpr (kFast) NMP_DOM(ok, 16, in(rahg, (T)NMP_DOM_RAHG_LO, (T)NMP_DOM_RAHG_HI));
-#endif
         const Recip<T> rrahg = d.rec(rahg), rrb = d.rec(rb);  // RAWG = RAHG
         T estv, destv;
         esat_sel(tdc(c.tv), estv, destv);
@@ -1621,9 +1500,6 @@ DEV void sflx_column(const DevParams& P, const KArgs<T>& A, Col<T>& c, const Sin
                         in(c.o2air, NMP_DOM_O2_LO, NMP_DOM_O2_HI) &&
                         (sp.fnf == L(0.0) || in(sp.fnf, NMP_DOM_FNF_LO, 1.0)) &&
                         apar_ok(parsun) && apar_ok(parsha);
-#ifdef NMP_STOMATA_FASTDIV
-              st_fast = true;  // (timing probe only: not exact in general)
-#endif
 #ifdef NMP_COUNT_FALLBACK
               if (!st_fast && (parsun > L(0.0) || parsha > L(0.0)))
                 atomicAdd(&nmp_fb_reason[24], 1u);  // stomata bisection on IEEE division
@@ -1646,10 +1522,8 @@ DEV void sflx_column(const DevParams& P, const KArgs<T>& A, Col<T>& c, const Sin
             canres<T, R>(V, c.sfcprs, c.tv, parsun, c.eah, btran, rssun, psnsun);
             canres<T, R>(V, c.sfcprs, c.tv, parsha, c.eah, btran, rssha, psnsha);
           }
-#ifndef NMP_VD_NOWIN
           if constexpr (kFast)
             NMP_DOM(ok, 17, in(rssun, L(0.0), (T)NMP_DOM_RS_HI) & in(rssha, L(0.0), (T)NMP_DOM_RS_HI));
-#endif
         }
         cah = d.divk(L(1.0), rrahc);
         cvh = d.divk(two_vaie, rrb);
@@ -1670,27 +1544,21 @@ DEV void sflx_column(const DevParams& P, const KArgs<T>& A, Col<T>& c, const Sin
         T bea = d.div(cew + ctw, rcond2);
         T cev = d.div((L(1.0) - bea) * cew * rhoair * CPAIR, rgammav);
         const T ctr_n = (L(1.0) - bea) * ctw * rhoair * CPAIR;
-#if NMP_VD_CHECKED & 1
         if constexpr (kFast) NMP_DOM(ok, 26, nwin(ctr_n));
-#endif
-        T ctr = dref.div(ctr_n, rgammav);
+        T ctr = d.div(ctr_n, rgammav);
         c.tah = ata + bta * c.tv;
         c.eah = aea + bea * estv;
         irc = fveg * (air + cir * p4(c.tv));
         shc = fveg * rhoair * CPAIR * cvh * (c.tv - c.tah);
         evc = d.div(fveg * rhoair * CPAIR * cew * (estv - c.eah), rgammav);
         const T tr_n = fveg * rhoair * CPAIR * ctw * (estv - c.eah);
-#if NMP_VD_CHECKED & 1
         if constexpr (kFast) NMP_DOM(ok, 27, nwin(tr_n));
-#endif
-        tr = dref.div(tr_n, rgammav);
+        tr = d.div(tr_n, rgammav);
         evc = rmin((c.tv > TFRZ) ? evlim_liq : evlim_ice, evc);
         T b = sav - irc - shc - evc - tr;
         T a = fveg * (L(4.0) * cir * p3(c.tv) + csh + (cev + ctr) * destv);
-#if NMP_VD_CHECKED & 1
         if constexpr (kFast) NMP_DOM(ok, 28, nwin(b));
-#endif
-        T dtv = dref.div(b, dref.rec(a));
+        T dtv = d.div(b, d.rec(a));
         irc = irc + fveg * L(4.0) * cir * p3(c.tv) * dtv;
         shc = shc + fveg * csh * dtv;
         evc = evc + fveg * cev * destv * dtv;
@@ -1704,7 +1572,8 @@ DEV void sflx_column(const DevParams& P, const KArgs<T>& A, Col<T>& c, const Sin
       if constexpr (kFast) NMP_DOM(ok, 18, in(c.tv, (T)NMP_DOM_T_LO, (T)NMP_DOM_T_HI));
       vtrips = 1;
       vege_iter(1, std::true_type{});  // iter 1 cannot exit (the test needs iter >= 5)
-      NMP_UNROLL(NMP_VEGE_UNROLL)
+      // not unrolled: x2 / x3 measured slower (profiles/r02/probes_optset.txt)
+#pragma unroll 1
       for (int iter = 2; iter <= 20; ++iter) {
         vtrips = iter;
         if constexpr (kFast) NMP_DOM(ok, 19, in(c.tv, (T)NMP_DOM_T_LO, (T)NMP_DOM_TV_HI));
@@ -1715,19 +1584,12 @@ DEV void sflx_column(const DevParams& P, const KArgs<T>& A, Col<T>& c, const Sin
       return ok;
     };
     DivRef<T> dr;
-#if NMP_VEGE_DIV
     if constexpr (sizeof(T) == 4 && R && OS != 0) {
       // the short exact division wherever the range proofs hold; a lane
       // outside their window repeats the loop from its start with IEEE
       // division (TV/TAH/EAH reloaded: nothing has stored them yet)
       DivFast32 df;
-#ifdef NMP_VD_NOFALLBACK
-      (void)vege_domain_ok();
-      vege_loop(df);
-      if (false) {  // (timing probe only: not exact in general)
-#else
       if (!vege_domain_ok() || !vege_loop(df)) {
-#endif
 #ifdef NMP_COUNT_FALLBACK
         atomicAdd(&nmp_fallback_ctr, 1u);
         for (int b = 0; b < 29; ++b)
@@ -1741,16 +1603,13 @@ DEV void sflx_column(const DevParams& P, const KArgs<T>& A, Col<T>& c, const Sin
     } else {
       vege_loop(dr);
     }
-#else
-    vege_loop(dr);
-#endif
     // under-canopy fluxes and TG (loop2, :2881-2914)
     air = -emg * (L(1.0) - emv) * c.lwdn - emg * emv * SB * p4(c.tv);
     cir = emg * SB;
     T csh = rhoair * CPAIR / rahg;
     T cev = rhoair * CPAIR / (gammag * (rahg + rsurf));
     T cgh = L(2.0) * df_top / dz_top;
-NMP_UNROLL(NMP_LOOP2_UNROLL)
+#pragma unroll 1
     for (int iter = 1; iter <= 5; ++iter) {
       tt = tdc(tgv);
       T destg;
@@ -1810,15 +1669,10 @@ NMP_UNROLL(NMP_LOOP2_UNROLL)
     // The bare-ground Newton loop (func.f90:3120-3200) with the division
     // policy `d`, as the canopy loop: every loop variable starts here, so a
     // lane outside the range proof's domain can run it again with IEEE
-    // division.  DTG = B/A: IEEE division, or with NMP_VD_CHECKED & 2 the
-    // loop's policy and a per-lane window on B.
+    // division.  DTG = B/A: the loop's policy too, behind a per-lane window
+    // on B (as the canopy loop's CTR, TR and DTV).
     auto bare_loop = [&](auto& d) -> bool {
       constexpr bool kFast = !std::is_same<std::decay_t<decltype(d)>, DivRef<T>>::value;
-#if NMP_VD_CHECKED & 2
-      auto& dref = d;
-#else
-      const DivRef<T> dref;
-#endif
       bool ok = true;
       auto in = [](T x, T lo, T hi) { return x >= lo && x <= hi; };
       [[maybe_unused]] auto nwin = [](T x) {
@@ -1836,7 +1690,9 @@ NMP_UNROLL(NMP_LOOP2_UNROLL)
       esat_sel(tdc(tgb), es_tgb, des_tgb);
       irb = shb = evb = ghb = L(0.0);
       const Sfc1Inv<T> invb = sfc1_inv(d, c.sfctmp, qair, rhoair, zlvl, zpdg, z0h);
-NMP_UNROLL(NMP_BARE_UNROLL)
+      // unrolled in the fp32 kernels: config #3 +0.8 %, fewer spills (59 -> 52);
+      // fp64 and the under-canopy loop2 measured no gain (profiles/r02/unroll_ab.txt)
+#pragma unroll sizeof(T) == 4 ? 5 : 1
       for (int iter = 1; iter <= 5; ++iter) {
         if constexpr (kFast) NMP_DOM(ok, 20, in(tgb, (T)NMP_DOM_T_LO, (T)NMP_DOM_TGB_HI));
         if (o.sfc == 1)
@@ -1864,10 +1720,8 @@ NMP_UNROLL(NMP_BARE_UNROLL)
         ghb = cgh * (tgb - stc_top);
         T b = sag - irb - shb - evb - ghb;
         T a = L(4.0) * cir * p3(tgb) + csh + cev * destg + cgh;
-#if NMP_VD_CHECKED & 2
         if constexpr (kFast) NMP_DOM(ok, 29, nwin(b));
-#endif
-        T dtg = dref.div(b, dref.rec(a));
+        T dtg = d.div(b, d.rec(a));
         irb = irb + L(4.0) * cir * p3(tgb) * dtg;
         shb = shb + csh * dtg;
         evb = evb + cev * destg * dtg;
@@ -1894,16 +1748,10 @@ NMP_UNROLL(NMP_BARE_UNROLL)
                          in(lgb.tmpch2, NMP_DOM_TMPC_LO, NMP_DOM_TMPC_HI));
       NMP_DOM(k, 23, in(zlvl - zpdg, NMP_DOM_DZ_LO, NMP_DOM_DZ_HI) &
                          in(z0mg, NMP_DOM_Z0_LO, NMP_DOM_Z0_HI) & in(rsurf, 0.0, NMP_DOM_RSURF_HI));
-#if NMP_VD_CHECKED & 2
       NMP_DOM(k, 30, in(emg, 0.0, 1.0) & in(cgh, 0.0, NMP_DOM_CGH_HI));  // DTG's A
-#endif
-#ifdef NMP_VD_NODOMAIN
-      k = true;
-#endif
       return k;
     };
     DivRef<T> drb;
-#if NMP_VEGE_DIV && NMP_BARE_DIV
     if constexpr (sizeof(T) == 4 && R && OS != 0) {
       DivFast32 dfb;
       if (!bare_domain_ok() || !bare_loop(dfb)) {
@@ -1917,9 +1765,6 @@ NMP_UNROLL(NMP_BARE_UNROLL)
     } else {
       bare_loop(drb);
     }
-#else
-    bare_loop(drb);
-#endif
     if (o.stc == 1 && c.snowh > L(0.05) && tgb > TFRZ) {
       tgb = TFRZ;
       irb = cir * p4(tgb) - emg * c.lwdn;
@@ -1941,11 +1786,6 @@ NMP_UNROLL(NMP_BARE_UNROLL)
     chb = ehb;
   }
 
-#if NMP_EARLY_LOADS & 1
-  // the water phase's fields issued here, their latency under aggregation,
-  // thermoprop, tsnosoi and phasechange
-  NMP_WATER_LOADS();
-#endif
   NMP_PHASE(6);
   // tile aggregation (:1246-1282)
   T fira, fsh, fgev, ssoil, fcev, fctr, t2m;
@@ -2035,9 +1875,9 @@ NMP_UNROLL(NMP_BARE_UNROLL)
     // the LDS slot index is laundered like fresh_state(): a real second read,
     // not the entry values kept live in registers through the flux loops
     int slot = threadIdx.x;
-    if constexpr (kPfReread<T, R>) __asm__ volatile("" : "+v"(slot));
+    if constexpr (kPrefetch<T, R>) __asm__ volatile("" : "+v"(slot));
     auto rd = [&](int f) -> T {
-      if constexpr (kPfReread<T, R>)
+      if constexpr (kPrefetch<T, R>)
         return lds_pool()[f * NMP_BLOCK + slot];
       else
         return gld(col_at(st, out.ld, out.col, f));
@@ -2328,16 +2168,14 @@ NMP_UNROLL(NMP_BARE_UNROLL)
   const T edir = qvap - qdew;
   out.template d<NMP_D_EDIR>(edir);
   out.s(NMP_S_SNEQVO, c.sneqvo);
-#ifdef NMP_TRUNC_ENERGY
-  return;  // timing experiment only (tools/build_variants.py): the energy phase alone
-#endif
 
   NMP_PHASE(9);
   // ===================== water: func.f90:4601-4804 =====================
   // fields first used by the water / carbon phase
-#if !(NMP_EARLY_LOADS & 1)
-  NMP_WATER_LOADS();
-#endif
+  const T prcp_w = out.la(NMP_A_PRCP), uu_w = out.la(NMP_A_UU), vv_w = out.la(NMP_A_VV);
+  c.zwt = out.ls(NMP_S_ZWT); c.wa = out.ls(NMP_S_WA); c.wt = out.ls(NMP_S_WT);
+  c.wslake = out.ls(NMP_S_WSLAKE);
+  c.slptyp = out.li(NMP_I_SLOPETYP);
   const T qprecc = L(0.10) * prcp_w;  // atm :517-518
   const T qprecl = L(0.90) * prcp_w;
   T ecan, etran, runsrf = L(0.0), runsub = L(0.0), qsnbot = L(0.0), ponding1 = L(0.0);
@@ -2702,7 +2540,7 @@ NMP_UNROLL(NMP_BARE_UNROLL)
 #pragma unroll
     for (int k = 0; k < 4; ++k) {
       const T e4 = (sizeof(T) == 4 && R) ? (T)A.c_exp_m4 : M::exp(-L(4.0));
-      if (NMP_UNFROZEN_FAST && c.sice[k] == L(0.0)) {
+      if (c.sice[k] == L(0.0)) {
         // no ice: FICE = 0, EXP(-4*(1-FICE)) = EXP(-4) = e4, so FCR = 0 exactly
         fcr[k] = L(0.0);
       } else {
@@ -2816,11 +2654,7 @@ NMP_UNROLL(NMP_BARE_UNROLL)
     // a = 0 or [2^-102, 2^100], so the quotient lies in [2^-122, 2^120]
     // (tools/div_proof.py soil_sites).  A lane outside takes IEEE division
     // (an exec-masked branch that no lane usually enters).
-#if NMP_SOIL_DIV
     constexpr bool kSoilFast = sizeof(T) == 4 && R && OS != 0;
-#else
-    constexpr bool kSoilFast = false;
-#endif
     typedef std::conditional_t<kSoilFast, DivFast32, DivRef<T>> SoilDiv;
     const SoilDiv sd;
     Recip<T> rtemp[3], rden[4], rnden[4];
@@ -3211,16 +3045,11 @@ NMP_UNROLL(NMP_BARE_UNROLL)
 // spills) for launches whose columns cannot fill more wave slots anyway:
 // config #2's 65,536 columns are one wave per SIMD (DESIGN.md "Small column
 // sets": fp64 0.158 -> 0.150 ms per step, fp32 0.130 -> 0.113).
-#ifndef NMP_WAVES_PER_EU
-#define NMP_WAVES_PER_EU 4
-#endif
-#ifndef NMP_WAVES_PER_EU_F64
-#define NMP_WAVES_PER_EU_F64 2
-#endif
+constexpr int kWavesPerEu = 4, kWavesPerEuF64 = 2;
 template <class T>
 constexpr int waves_per_eu(bool small) {
-  return sizeof(T) == 4 ? (small ? NMP_WAVES_PER_EU / 2 : NMP_WAVES_PER_EU)
-                        : (small ? (NMP_WAVES_PER_EU_F64 + 1) / 2 : NMP_WAVES_PER_EU_F64);
+  return sizeof(T) == 4 ? (small ? kWavesPerEu / 2 : kWavesPerEu)
+                        : (small ? kWavesPerEuF64 / 2 : kWavesPerEuF64);
 }
 // the LDS layer copy's completion is explicit: LDS-DMA loads count in
 // vmcnt, and the "memory" clobber keeps every LDS read of the copied fields
@@ -3228,9 +3057,7 @@ constexpr int waves_per_eu(bool small) {
 // below the wait
 template <class T, bool R>
 DEV void lds_copy_wait() {
-#if NMP_LDS_EXPLICIT_WAIT
   if constexpr (kPrefetch<T, R>) __asm__ volatile("s_waitcnt vmcnt(0)" ::: "memory");
-#endif
 }
 
 // The loads of column c0 into `Col<T> c` and the column's output sink `out`,
@@ -3266,7 +3093,7 @@ DEV void lds_copy_wait() {
   {                                                                                          \
     lds_copy_wait<T, R>();                                                                   \
     auto rd = [&](int f) -> T {                                                              \
-      if constexpr (kPfEntry<T, R>)                                                          \
+      if constexpr (kPrefetch<T, R>)                                                         \
         return lds_pool()[f * NMP_BLOCK + threadIdx.x];                                      \
       else                                                                                   \
         return out.ls(f);                                                                    \
@@ -3293,9 +3120,6 @@ void sflx_step_kernel(const DevParams* __restrict__ gparams,
 #ifdef NMP_WAVE_TIMING
   const unsigned long long wt0 = __builtin_amdgcn_s_memrealtime();
 #endif
-#ifdef NMP_PARAMS_GLOBAL
-  const DevParams& sp = *gparams;
-#else
   __shared__ __attribute__((aligned(16))) DevParams sp;
   {
     const int4* src = reinterpret_cast<const int4*>(gparams);
@@ -3305,7 +3129,6 @@ void sflx_step_kernel(const DevParams* __restrict__ gparams,
   }
   if constexpr (sizeof(T) == 4 && R) stage_math_tables();
   __syncthreads();
-#endif
   int64_t blk = blockIdx.x;
   if (a.order) {
     // re-binned launch: workgroups are dealt round-robin over the 8 XCDs
@@ -3429,8 +3252,6 @@ extern "C" int nmp_debug_phase_cycles(unsigned long long* out16, int reset) {
 }
 #endif
 #endif
-
-
 
 #if defined(NMP_COUNT_FALLBACK) && (!defined(NMP_TU) || NMP_TU == 4)
 // (probe builds) lanes that left the range proof's domain and re-ran the

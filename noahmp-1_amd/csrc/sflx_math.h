@@ -18,70 +18,24 @@
 
 #include "glibc_math.h"
 
-// Math wrappers are inlined by default; -DNMP_MATH_OUTLINE keeps one copy of
-// each (smaller code, fewer instruction-cache misses, call overhead instead).
-#ifdef NMP_MATH_OUTLINE
-#define NMP_MATH_FN static __device__ __noinline__
-#else
 #define NMP_MATH_FN static __device__ __forceinline__
-#endif
 
 namespace nmp {
 
 template <class T, bool REF>
 struct Mth;
 
-// fp64 exp with a short dependent chain (NMP_F64_EXP_ESTRIN): ocml's own
-// reduction (k = rint(x/ln2), r = x - k ln2 in two parts) and its degree-11
-// Taylor coefficients, but the polynomial evaluated by Estrin's scheme (depth
-// 4 instead of 11 dependent FMAs) and rebuilt with ldexp.  The fp64 path is
-// held to tolerances, not bits (DESIGN.md "fp64"); the result is within an ulp
-// or two of ocml's.  Aimed at config #2, whose one wave per SIMD runs every
-// dependent chain at full latency.
-#ifndef NMP_F64_EXP_ESTRIN
-#define NMP_F64_EXP_ESTRIN 0
-#endif
-__device__ __forceinline__ double exp_estrin(double x) {
-  const double k = __builtin_rint(x * 1.4426950408889634);     // x / ln2
-  double r = __builtin_fma(k, -0.6931471805599453, x);          // ln2, then its tail
-  r = __builtin_fma(k, -2.3190468138462996e-17, r);
-  const double r2 = r * r, r4 = r2 * r2, r8 = r4 * r4;
-  // ocml's coefficients c0..c11 (c0 = c1 = 1), paired by Estrin's scheme
-  const double q0 = __builtin_fma(r, 1.0, 1.0);
-  const double q1 = __builtin_fma(r, 0.16666666666666477, 0.5000000000000012);
-  const double q2 = __builtin_fma(r, 0.008333333333455043, 0.041666666666519754);
-  const double q3 = __builtin_fma(r, 0.00019841269589115522, 0.0013888888945916382);
-  const double q4 = __builtin_fma(r, 2.755751454582531e-06, 2.480149103909504e-05);
-  const double q5 = __builtin_fma(r, 2.502232256764614e-08, 2.7630903490112654e-07);
-  const double s0 = __builtin_fma(r2, q1, q0);
-  const double s1 = __builtin_fma(r2, q3, q2);
-  const double s2 = __builtin_fma(r2, q5, q4);
-  const double p = __builtin_fma(r8, s2, __builtin_fma(r4, s1, s0));
-  const double e = __builtin_ldexp(p, (int)k);
-  // ocml's limits: +inf above 1024, 0 below -1075 (ldexp saturates between);
-  // NaN propagates through r
-  return x > 1024.0 ? __builtin_inf() : (x < -1075.0 ? 0.0 : e);
-}
-
 template <bool REF>
 struct Mth<double, REF> {
-#if NMP_F64_EXP_ESTRIN
-  NMP_MATH_FN double exp(double x) { return exp_estrin(x); }
-#else
   NMP_MATH_FN double exp(double x) { return ::exp(x); }
-#endif
   NMP_MATH_FN double exp2(double x) { return ::exp2(x); }
   NMP_MATH_FN double log(double x) { return ::log(x); }
   NMP_MATH_FN double log10(double x) { return ::log10(x); }
-#ifdef NMP_F64_OCML_POW
-  NMP_MATH_FN double pow(double x, double y) { return ::pow(x, y); }
-#else
   // x**y as exp(y log x): within |y log x| ulp of pow, which is far inside the
   // fp64 path's tolerances, at about half the cost of ocml's double pow (that
   // one carries log x in double-double).  Every base in the kernel is >= 0;
   // 0**y (y > 0) -> exp(-inf) = 0 as pow gives.
   NMP_MATH_FN double pow(double x, double y) { return exp(y * ::log(x)); }
-#endif
   // x**0.25 and x**(-0.25): the fp64 path is held to a tolerance, not to bits
   // (DESIGN.md "fp64"), so the fourth root is two square roots (<= 1 ulp from
   // pow, and ~10x cheaper than ocml's double pow)
@@ -117,13 +71,6 @@ struct Mth<float, false> {
 static __shared__ gm::GmTables gm_lds;
 static __constant__ gm::GmTables gm_const = {GM_EXP2F_TAB, GM_LOGF_TAB, GM_POWF_TAB};
 
-// NMP_PARAMS_GLOBAL (probe builds): the tables are read from global memory
-// (L1/L2-resident) instead of being staged per workgroup into LDS
-#ifdef NMP_PARAMS_GLOBAL
-#define NMP_GM_TAB gm_const
-#else
-#define NMP_GM_TAB gm_lds
-#endif
 __device__ __forceinline__ void stage_math_tables() {
   constexpr int NW = sizeof(gm::GmTables) / sizeof(int4);
   static_assert(sizeof(gm::GmTables) % sizeof(int4) == 0, "table size");
@@ -134,14 +81,14 @@ __device__ __forceinline__ void stage_math_tables() {
 
 template <>
 struct Mth<float, true> {
-  NMP_MATH_FN float exp(float x) { return gm::expf(x, NMP_GM_TAB); }
-  NMP_MATH_FN float exp2(float x) { return gm::exp2f(x, NMP_GM_TAB); }
-  NMP_MATH_FN float log(float x) { return gm::logf(x, NMP_GM_TAB); }
-  NMP_MATH_FN float log10(float x) { return gm::log10f(x, NMP_GM_TAB); }
-  NMP_MATH_FN float pow(float x, float y) { return gm::powf(x, y, NMP_GM_TAB); }
+  NMP_MATH_FN float exp(float x) { return gm::expf(x, gm_lds); }
+  NMP_MATH_FN float exp2(float x) { return gm::exp2f(x, gm_lds); }
+  NMP_MATH_FN float log(float x) { return gm::logf(x, gm_lds); }
+  NMP_MATH_FN float log10(float x) { return gm::log10f(x, gm_lds); }
+  NMP_MATH_FN float pow(float x, float y) { return gm::powf(x, y, gm_lds); }
   // bit-exact fp32: the reference's powf itself
-  NMP_MATH_FN float pow_q(float x) { return gm::powf(x, 0.25f, NMP_GM_TAB); }
-  NMP_MATH_FN float pow_mq(float x) { return gm::powf(x, -0.25f, NMP_GM_TAB); }
+  NMP_MATH_FN float pow_q(float x) { return gm::powf(x, 0.25f, gm_lds); }
+  NMP_MATH_FN float pow_mq(float x) { return gm::powf(x, -0.25f, gm_lds); }
   NMP_MATH_FN float tanh(float x) { return gm::tanhf(x); }
   NMP_MATH_FN float atan(float x) { return gm::atanf(x); }
   NMP_MATH_FN float tan(float x) { return gm::tanf(x); }
@@ -153,26 +100,18 @@ struct Mth<float, true> {
 // x**y1 and x**y2 with one base (wdfcnd1/wdfcnd2's WDF and WCND): each equal
 // to Mth::pow's result bit for bit.  The fp32 "ref" path forms powf's log2 of
 // x once (gm::powf_pair); the fp64 path (exp(y log x)) its log once.
-// NMP_POW_PAIR=0: two independent calls (A/B probe).
-#ifndef NMP_POW_PAIR
-#define NMP_POW_PAIR 1
-#endif
 template <class T, bool R>
 __device__ __forceinline__ void pow_pair(T x, T y1, T y2, T& r1, T& r2) {
-#if NMP_POW_PAIR
   if constexpr (sizeof(T) == 4 && R) {
-    gm::powf_pair(x, y1, y2, NMP_GM_TAB, r1, r2);
+    gm::powf_pair(x, y1, y2, gm_lds, r1, r2);
     return;
   }
-#ifndef NMP_F64_OCML_POW
   if constexpr (sizeof(T) == 8) {
     const double lx = ::log(x);
     r1 = Mth<double, R>::exp(y1 * lx);
     r2 = Mth<double, R>::exp(y2 * lx);
     return;
   }
-#endif
-#endif
   r1 = Mth<T, R>::pow(x, y1);
   r2 = Mth<T, R>::pow(x, y2);
 }
@@ -191,10 +130,6 @@ __device__ __forceinline__ T p4(T x) { return x * p3(x); }
 template <class T>
 __device__ __forceinline__ T p5(T x) { return x * p4(x); }
 
-// NMP_SQRT_SHORT=0: the range-proven sqrt sites keep the IEEE lowering (A/B probe)
-#ifndef NMP_SQRT_SHORT
-#define NMP_SQRT_SHORT 1
-#endif
 // Division in the Newton loops (vege_flux, bare_flux, sfcdif1, ragrb).  fp32
 // (the bit-exact path): IEEE `/`, except at the range-proven sites that go
 // through DivFast32 (below).  fp64 (held to tolerances, not bits): the
@@ -216,44 +151,8 @@ template <class T>
 __device__ __forceinline__ T dv(T a, T b) {
   return a / b;
 }
-#if defined(NMP_F32_DIV) && NMP_F32_DIV == 1
-// candidate: the IEEE lowering with ONE residual correction instead of two
-template <>
-__device__ __forceinline__ float dv<float>(float a, float b) {
-  bool num_scaled;
-  const float den = __builtin_amdgcn_div_scalef(a, b, false, &num_scaled);
-  const float num = __builtin_amdgcn_div_scalef(a, b, true, &num_scaled);
-  float r = __builtin_amdgcn_rcpf(den);
-  const float e0 = __builtin_fmaf(-den, r, 1.0f);
-  r = __builtin_fmaf(e0, r, r);
-  const float q = num * r;
-  const float e = __builtin_fmaf(-den, q, num);
-  return __builtin_amdgcn_div_fixupf(__builtin_amdgcn_div_fmasf(e, r, q, num_scaled), b, a);
-}
-#elif defined(NMP_F32_DIV)
-// timing probes of shorter fp32 division sequences (tools only, NOT shipped):
-// 9 = v_rcp + one Newton step + two residual corrections + div_fixup (the IEEE
-// sequence without div_scale / div_fmas), 7 = one residual correction
-template <>
-__device__ __forceinline__ float dv<float>(float a, float b) {
-  float r = __builtin_amdgcn_rcpf(b);
-  float e = __builtin_fmaf(-b, r, 1.0f);
-  r = __builtin_fmaf(e, r, r);
-  float q = a * r;
-  e = __builtin_fmaf(-b, q, a);
-  q = __builtin_fmaf(e, r, q);
-#if NMP_F32_DIV == 9
-  e = __builtin_fmaf(-b, q, a);
-  q = __builtin_fmaf(e, r, q);
-#endif
-  return __builtin_amdgcn_div_fixupf(q, b, a);
-}
-#endif
 template <>
 __device__ __forceinline__ double dv<double>(double a, double b) {
-#ifdef NMP_F64_IEEE_DIV
-  return a / b;
-#else
   double r = __builtin_amdgcn_rcp(b);
   double e = __builtin_fma(-b, r, 1.0);
   r = __builtin_fma(r, e, r);
@@ -262,12 +161,7 @@ __device__ __forceinline__ double dv<double>(double a, double b) {
   double q = a * r;
   e = __builtin_fma(-b, q, a);
   q = __builtin_fma(e, r, q);
-#ifdef NMP_F64_DV_NOGUARD
-  return q;
-#else
   return __builtin_amdgcn_div_fixup(q, b, a);
-#endif
-#endif
 }
 
 // ---------------------------------------------------------------------------
@@ -342,18 +236,6 @@ struct DivFast32 {
     const float e = __builtin_fmaf(-b, r, 1.0f);
     return __builtin_fmaf(e, r, r);
   }
-#ifdef NMP_DIV_NOSHARE
-  // (probe) no shared reciprocal: each quotient forms its own (fewer live
-  // registers, three more instructions per division)
-  __device__ __forceinline__ Recip<float> rec(float b) const { return {b, b}; }
-  __device__ __forceinline__ float div(float a, const Recip<float>& R) const {
-    const float r = recip(R.b);
-    float q = a * r;
-    const float e = __builtin_fmaf(-R.b, q, a);
-    q = __builtin_fmaf(e, r, q);
-    return __builtin_amdgcn_div_fixupf(q, R.b, a);
-  }
-#else
   __device__ __forceinline__ Recip<float> rec(float b) const { return {b, recip(b)}; }
   __device__ __forceinline__ float div(float a, const Recip<float>& R) const {
     float q = a * R.r;
@@ -361,17 +243,10 @@ struct DivFast32 {
     q = __builtin_fmaf(e, R.r, q);
     return __builtin_amdgcn_div_fixupf(q, R.b, a);
   }
-#endif
   __device__ __forceinline__ float divk(float a, const Recip<float>& R) const { return div(a, R); }
   __device__ __forceinline__ void chk(float) const {}
   // at the range-proven sqrt sites (tools/div_proof.py): x finite and >= 2^-96
-  __device__ __forceinline__ static float sqrt(float x) {
-#if NMP_SQRT_SHORT
-    return sqrt_normal32(x);
-#else
-    return ::sqrtf(x);
-#endif
-  }
+  __device__ __forceinline__ static float sqrt(float x) { return sqrt_normal32(x); }
 };
 
 // Register-array access with a runtime index, lowered to a select chain so the
@@ -381,29 +256,18 @@ struct DivFast32 {
 // forces the whole enclosing aggregate (the column struct) into scratch.
 template <class T>
 __device__ __forceinline__ T pin(T v) {
-#ifdef NMP_PIN_NONVOLATILE
-  __asm__("" : "+v"(v));
-#else
   __asm__ volatile("" : "+v"(v));
-#endif
   return v;
 }
 template <class T, int N>
 __device__ __forceinline__ T dget(const T (&a)[N], int i) {
   T r = pin(a[0]);
-#ifdef NMP_DGET_BRANCHY
-  // (A/B only) the pin inside the select: the volatile asm cannot be
-  // speculated, so every element becomes an exec-masked branch
-#pragma unroll
-  for (int k = 1; k < N; ++k) r = (i == k) ? pin(a[k]) : r;
-#else
   // every element pinned unconditionally, then selected: one v_cndmask each
 #pragma unroll
   for (int k = 1; k < N; ++k) {
     const T v = pin(a[k]);
     r = (i == k) ? v : r;
   }
-#endif
   return r;
 }
 template <class T, int N>
@@ -412,28 +276,6 @@ __device__ __forceinline__ void dset(T (&a)[N], int i, T v) {
   for (int k = 0; k < N; ++k)
     if (i == k) a[k] = v;
 }
-// LDS-resident per-lane arrays (NMP_LDS_WORK): element k of lane t lives at
-// pool[(SLOT + k) * NMP_BLOCK + t], i.e. [array][layer][lane] -- consecutive
-// lanes hit consecutive banks, a runtime layer index is one address add, and
-// the array holds no VGPRs across the step.  Each lane touches only its own
-// column, so no barrier is needed.
-template <class T>
-__device__ __forceinline__ T* lds_lane_pool() {
-  __shared__ T pool[NMP_LDS_SLOTS * NMP_BLOCK];
-  return pool + threadIdx.x;
-}
-template <class T, int N, int SLOT>
-struct LArr {
-  static_assert(SLOT + N <= NMP_LDS_SLOTS, "LDS slot pool too small");
-  __device__ __forceinline__ T& operator[](int k) const {
-    return lds_lane_pool<T>()[(SLOT + k) * NMP_BLOCK];
-  }
-};
-template <class T, int N, int S>
-__device__ __forceinline__ T dget(const LArr<T, N, S>& a, int i) { return a[i]; }
-template <class T, int N, int S>
-__device__ __forceinline__ void dset(const LArr<T, N, S>& a, int i, T v) { a[i] = v; }
-
 __device__ __forceinline__ float zget(const float (&a)[4], int i) {
   return i == 0 ? a[0] : i == 1 ? a[1] : i == 2 ? a[2] : a[3];
 }

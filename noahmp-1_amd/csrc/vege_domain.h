@@ -126,8 +126,8 @@
 #endif
 // The numerators of CTR, TR and DTV = B/A (canopy loop) and DTG = B/A (bare
 // loop) are products and sums of several possibly small terms that no static
-// bound keeps away from the subnormals; with NMP_VD_CHECKED they are checked
-// per lane every iteration instead: 0, or 2^NUM_LO_EXP <= |x| <= 2^NUM_HI_EXP
+// bound keeps away from the subnormals; they are checked per lane every
+// iteration instead: 0, or 2^NUM_LO_EXP <= |x| <= 2^NUM_HI_EXP
 // (a lane outside re-runs its loop with IEEE division).  The ground emissivity
 // EMG lies in [0, 1] and the bare loop's CGH = 2*DF/DZ of the top layer in
 // [0, CGH_HI], both checked once per column: they bound the denominators A.

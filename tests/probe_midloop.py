@@ -12,7 +12,7 @@ division from restored inputs (sflx_kernel.hip vege_loop / bare_loop).  Every
 column must still equal the C restatement of the reference bit for bit, in
 both occupancy instantiations and at diagnostics levels NONE and FULL, and
 the device counter must show the in-loop windows fired.  A dry-clay set sends
-soil-water sub-step divisions (NMP_SOIL_DIV) below DivFast32's exact region:
+soil-water sub-step divisions (sflx_kernel.hip kSoilFast) below DivFast32's exact region:
 they must take IEEE division (counted) and stay bit-exact.
 
     NOAHMP_ENGINE_LIB=.../lib_probe_midloop.so python tests/probe_midloop.py
@@ -88,7 +88,7 @@ def main():
                 res["runs"].append(run)
                 ok_all = ok_all and bool(ok.all() and fb > 0 and why[19] > 0 and why[20] > 0
                                          and why[28] > 0 and why[29] > 0)
-    # soil water (NMP_SOIL_DIV): very dry clay (SOILTYP 12, BEXP 11.55) makes
+    # soil water (kSoilFast): very dry clay (SOILTYP 12, BEXP 11.55) makes
     # WDF * DDZ fall below 2^-102, outside DivFast32's exact region: those
     # divisions must take IEEE division (fb_reason[25]) and every column keep
     # the reference's bits

@@ -221,7 +221,7 @@ def stomata_sites(D, T, p, es, rb):
 
 def soil_sites():
     """The soil-water sub-steps' divisions by the layer thicknesses (srt,
-    func.f90:6238-6276; sflx_kernel.hip NMP_SOIL_DIV).  Their denominators are
+    func.f90:6238-6276; sflx_kernel.hip kSoilFast).  Their denominators are
     launch-uniform differences of ZSOIL, which the kernel checks once against
     [2^-20, 2^20] (outside: every such division on IEEE).  Their numerators
     (2, 2*(SMX(K)-SMX(K+1)), WDF*DDZ, WFLUX) are not bounded away from 0 --
@@ -359,7 +359,7 @@ def main():
     hg_q = site("HG = RHOAIR*CPAIR*(TG-TAH) / RAHG", rhocp * dT, rahg, ":2865")
     site("QSFC = 0.622*EAH / (SFCPRS-0.378*EAH)", 0.622 * eah,
          M(p.lo - 0.378 * eah.hi, p.hi), ":2868")
-    # ---- CTR, TR, DTV = B/A (NMP_VD_CHECKED): the numerators are checked per
+    # ---- CTR, TR, DTV = B/A (sflx_kernel.hip nwin): the numerators are checked per
     # lane every iteration (vege_domain.h NUM_LO_EXP / NUM_HI_EXP); the
     # denominators are bounded here.  A = FVEG*(4*CIR*TV**3 + CSH + (CEV+CTR)*DESTV),
     # every term >= 0: CIR = (2 - EMV*(1-EMG))*EMV*SB with EMG in [0, 1] (checked)

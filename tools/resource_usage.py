@@ -2,7 +2,7 @@
 instantiations (hipcc -Rpass-analysis=kernel-resource-usage), compiled with the
 engine's flags plus any extra ones given on the command line.
 
-    python tools/resource_usage.py [-DNMP_WAVES_PER_EU=5 ...]
+    python tools/resource_usage.py [-DNMP_BLOCK=128 ...]
 """
 import os
 import re

@@ -1,5 +1,5 @@
 """How full do the wave slots stay during a step?  (GPU box; variant libraries
-built with -DNMP_WAVE_TIMING, tools/build_variants.py wt wt_b128 wt_b64.)
+built with -DNMP_WAVE_TIMING, tools/build_variants.py wt.)
 
 Runs the bench workload (config #3 columns in the coherent order, resident
 forcing) for a few steps with S stream ranges, reads every wave's
