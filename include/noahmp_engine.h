@@ -27,6 +27,8 @@
  * nmp_accumulate,             interval totals / means of the output fluxes and the water
  *   nmp_water_storage,        budget's closure: BEG_WB / END_WB / ERRWAT, which the reference
  *   nmp_accum_finish          forms and drops             core/module_noahmp_func.f90:339-344, 723-731
+ * nmp_region_reduce           no counterpart: weighted sums / means of an output block's fields
+ *                             over the columns of each region (basin means), on the device
  * nmp_frh2o, nmp_frh2o_host   frh2o (public routine)        core/module_noahmp_func.f90:4494-4598
  * nmp_calhum, nmp_calhum_host calhum (public by default)     core/module_noahmp_func.f90:3958-3984
  * nmp_state_from_aos          layout bridge from noahmp_state_t records
@@ -418,6 +420,55 @@ int nmp_water_storage(nmp_engine* eng, int64_t ncol, int64_t ld, const void* sta
                       const int32_t* isnow, const int32_t* static_i, void* storage, void* stream);
 int nmp_accum_finish(nmp_engine* eng, int64_t ncol, int64_t ld, double span_s, double* acc,
                      const void* stor_end, void* stor_beg, void* out, void* stream);
+
+/* Region-aggregated output (no counterpart in the reference): for each of
+ * nfield fields of the field-major block `fields` (engine precision T,
+ * fields[f*ld + c], ncol columns; e.g. nmp_step's diag or an output step's
+ * 35-field block) the weighted sum, and optionally the weighted mean, over the
+ * columns of each of nreg regions.  The summation tree is fixed by the plan
+ * below and is part of this interface: the result's bits do not depend on the
+ * launch shape, the stream, the world size or anything but the plan and the
+ * values, and a host can restate them.  All arithmetic is IEEE double, each
+ * operation rounded once (no fused multiply-add), no atomics.
+ *
+ * Plan (built once by the caller; device arrays):
+ *  - The columns of a region are listed in ascending column order, region
+ *    after region; each region's list is padded to a multiple of
+ *    NMP_REGION_CHUNK = 256 entries.  entry_col[e] (int32) is entry e's column,
+ *    -1 for a pad; entry_w[e] (double) its weight, 0 for a pad.  A *chunk* is
+ *    256 consecutive entries; there are nchunk of them (nchunk*256 entries).
+ *  - region_chunk0[nreg+1] (int64): region r owns chunks region_chunk0[r] ..
+ *    region_chunk0[r+1]-1.  A region without columns owns no chunk.
+ *  - wsum[nreg] (double): the divisor of the means -- by convention the same
+ *    tree applied to a field of ones, i.e. to the weights.
+ * Pass 1, per chunk k and field f, as 64 lanes: lane l starts at x = +0.0 and
+ * for j = 0, 1, 2, 3 in this order takes entry e = 256 k + 64 j + l; if
+ * entry_col[e] >= 0: x = x + (double)fields[f*ld + entry_col[e]] * entry_w[e]
+ * (one rounded product, then one add).  A pad entry is skipped: its value is
+ * never loaded nor multiplied, so no NaN*0 arises from it (an entry_col >= ncol
+ * is skipped likewise).  Then, for s = 32, 16, 8, 4, 2, 1:
+ * x[l] = x[l] + x[l xor s] for every lane; partial[f*nchunk + k] = x[0].
+ * With a the 64 lane values, that is numpy's
+ *   for s in (32, 16, 8, 4, 2, 1): a = a[:s] + a[s:2*s]
+ * Pass 2, per region r and field f: sum = +0.0; for k = region_chunk0[r] ..
+ * region_chunk0[r+1]-1 in this order: sum = sum + partial[f*nchunk + k];
+ * sums[f*nreg + r] = sum and, where means is not NULL,
+ * means[f*nreg + r] = sum / wsum[r] (one division).  A region without chunks
+ * gives sum +0.0 and, with wsum 0, mean NaN (0/0).
+ * Values reduce as they are: a NaN column makes its region's sum NaN (and no
+ * other's), and the night-time ALBEDO = -999.9 (hazard H8) enters a mean as
+ * that number; nothing is masked.
+ * partial is caller scratch of nfield*nchunk doubles; sums and means are
+ * nfield*nreg doubles.  Device pointers; both passes are enqueued on `stream`
+ * in that order and the call neither synchronises nor allocates.  NMP_E_ARG
+ * for nfield < 1, ld < ncol, a negative count or a NULL pointer other than
+ * means; nchunk == 0 or nreg == 0 is NMP_OK with nothing enqueued. */
+enum { NMP_REGION_CHUNK = 256 };
+int nmp_region_reduce(nmp_engine* eng, int64_t ncol, int64_t ld, int nfield, const void* fields,
+                      int64_t nchunk, const int32_t* entry_col, const double* entry_w,
+                      int64_t nreg, const int64_t* region_chunk0, const double* wsum,
+                      double* partial, double* sums, double* means /* may be NULL */,
+                      void* stream);
 
 int nmp_run(nmp_engine* eng, int64_t ncol, int64_t ld, const float zsoil[4], float dt,
             float julian0, int32_t yearlen, int32_t nsteps, void* state, int32_t* isnow,

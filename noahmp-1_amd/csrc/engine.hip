@@ -47,6 +47,9 @@ namespace {
 // largest column stride: the kernels form a column's byte offset from a
 // field's base in 32 bits (2^29 columns of 8-byte fp64 values = 4 GiB)
 constexpr int64_t kMaxColumns = int64_t(1) << 29;
+// most fields one nmp_region_reduce call takes (its launches count
+// nreg x nfield threads in 64 bits and blocks in 32)
+constexpr int kMaxRegionFields = 1024;
 
 bool options_ok(const nmp_options& o) {
   // valid values of each option (core/module_noahmp_global.f90:17-74)
@@ -455,6 +458,27 @@ int nmp_accum_finish(nmp_engine* eng, int64_t ncol, int64_t ld, double span_s, d
   if (ensure_device(eng->device) != NMP_OK) return NMP_E_DEVICE;
   return nmp::launch_accum_finish(eng->precision, ncol, ld, span_s, acc, stor_end, stor_beg, out,
                                   static_cast<hipStream_t>(stream)) == hipSuccess
+             ? NMP_OK
+             : NMP_E_DEVICE;
+}
+
+int nmp_region_reduce(nmp_engine* eng, int64_t ncol, int64_t ld, int nfield, const void* fields,
+                      int64_t nchunk, const int32_t* entry_col, const double* entry_w,
+                      int64_t nreg, const int64_t* region_chunk0, const double* wsum,
+                      double* partial, double* sums, double* means, void* stream) {
+  if (!eng || ncol < 0 || ld < ncol || ld >= kMaxColumns || nfield < 1 ||
+      nfield > kMaxRegionFields || nchunk < 0 || nchunk >= kMaxColumns || nreg < 0 ||
+      nreg >= kMaxColumns || nreg * nfield / 256 >= INT32_MAX)
+    return NMP_E_ARG;
+  if (nchunk == 0 || nreg == 0) return NMP_OK;
+  if (!fields || !entry_col || !entry_w || !region_chunk0 || !wsum || !partial || !sums)
+    return NMP_E_ARG;
+  if (ensure_device(eng->device) != NMP_OK) return NMP_E_DEVICE;
+  // the two passes of one call are enqueued back to back
+  std::lock_guard<std::mutex> lk(eng->host_mu);
+  return nmp::launch_region_reduce(eng->precision, ncol, ld, nfield, fields, nchunk, entry_col,
+                                   entry_w, nreg, region_chunk0, wsum, partial, sums, means,
+                                   static_cast<hipStream_t>(stream)) == hipSuccess
              ? NMP_OK
              : NMP_E_DEVICE;
 }

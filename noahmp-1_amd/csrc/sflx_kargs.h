@@ -82,6 +82,15 @@ hipError_t launch_accum_finish(int precision, int64_t ncol, int64_t ld, double s
                                const void* stor_end, void* stor_beg, void* out,
                                hipStream_t stream);
 
+// csrc/regions.hip: deterministic segmented weighted reduction of a field-major
+// block over the plan's regions (pass 1: chunk partials, pass 2: region sums
+// and means), both enqueued on `stream` in that order
+hipError_t launch_region_reduce(int precision, int64_t ncol, int64_t ld, int nfield,
+                                const void* fields, int64_t nchunk, const int32_t* entry_col,
+                                const double* entry_w, int64_t nreg, const int64_t* region_chunk0,
+                                const double* wsum, double* partial, double* sums, double* means,
+                                hipStream_t stream);
+
 // csrc/routines.hip: the reference's public routines frh2o / calhum over n
 // elements (device pointers, engine precision; math 0 = the fp32 "ref" policy)
 hipError_t launch_frh2o(int precision, int math, const DevParams* P, int64_t n,

@@ -18,6 +18,9 @@ offline/noahmp_config.py has no time loop, forcing reader or writer, SURVEY
   with ``accumulate=True`` each file also carries the interval's accumulated
   output (layout.BUDGET: means, totals and the water budget's closure, added up
   on the device after every step: nmp_accumulate / nmp_accum_finish);
+  with ``regions`` each output step also writes the regions' weighted means of
+  every output field as ``<YYYYMMDDHH>.REGIONS_DOMAIN1`` (nmp_region_reduce on
+  the output block, on rank 0; ``write_grids=False`` then drops the grids);
 * restart steps (Config.restart_frequency, calendar months allowed) write the
   complete SoA state (``RESTART.<YYYYMMDDHH>_DOMAIN1.nc`` on a grid, else
   ``.npz``), which `load_restart` reads back -- the state SoA *is* the restart
@@ -64,6 +67,7 @@ import torch
 import torch.distributed as dist
 
 from . import cases, layout as L, ncio, shard, timeman
+from .regions import RegionPlan, area_weights
 from .config import Config
 from .engine import ColumnState, Engine, StreamShards
 from .order import coherent_order
@@ -190,12 +194,39 @@ def _global_count(n: int, dev) -> int:
     return int(t.item())
 
 
+def region_columns(path: str, grid: ncio.Grid, perm: np.ndarray | None = None,
+                   weights="area"):
+    """(region id, weight) of every engine column from a region file on the
+    run's grid (ncio.read_region_map): the grid's land points, laid out in the
+    engine's column order `perm` (land point of each column; None = grid
+    order) like every other per-column input.  A point off the land mask is no
+    column; a column with REGION < 0 is in no region.  weights: "area" = the
+    file's AREA if it has one, else cos(latitude) in double; "equal" = 1; an
+    array = one weight per land point in grid order, taken as given."""
+    reg, area = ncio.read_region_map(path, grid)
+    if isinstance(weights, str):
+        if weights == "area":
+            w = area if area is not None else area_weights(grid.lat_rad)
+        elif weights == "equal":
+            w = np.ones(grid.n, np.float64)
+        else:
+            raise ValueError(f"region_weights must be 'area', 'equal' or an array, not {weights!r}")
+    else:
+        w = np.asarray(weights, np.float64)
+        if w.shape != (grid.n,):
+            raise ValueError(f"region weights must have shape ({grid.n},), not {w.shape}")
+    if perm is None:
+        return reg, w
+    return reg[perm], w[perm]
+
+
 class OfflineDriver:
     def __init__(self, cfg: Config, cols: cases.ColumnSet, device: int = 0,
                  params: Params | None = None, forcing=None, precision: int = 4,
                  math: str = "ref", zsoil=cases.CASE_NML_ZSOIL, write: bool = True,
                  streams: int = 2, grid: ncio.Grid | None = None, ldasin_upload: bool = True,
-                 cosz: str = "device", ingest: bool = True, accumulate: bool = False):
+                 cosz: str = "device", ingest: bool = True, accumulate: bool = False,
+                 regions=None, region_weights="area", write_grids: bool = True):
         """cols: this rank's columns (all of them on a single rank); under an
         initialised process group they must be the rank's shard_range block of
         the global column set.  ldasin_upload: with a provider that has
@@ -215,7 +246,19 @@ class OfflineDriver:
         writes its fluxes (DIAG_OUT_LEVEL) and nmp_accumulate adds them up on
         the range's stream right after the step; output steps also close the
         interval there (nmp_water_storage, nmp_accum_finish).  Off (the
-        default), every code path and output byte is as without it."""
+        default), every code path and output byte is as without it.
+        regions: per-column int region ids in the order of `cols` (< 0: in no
+        region); under a process group, of the global column set in global
+        column order (rank 0 reduces the gathered block, so the sums' bytes do
+        not depend on the world size).  Output steps then also write the
+        regions' weighted means of every output field (REGIONS files,
+        ncio.write_regions), reduced on the device from the output block
+        (nmp_region_reduce).  region_weights: "area" = cos(latitude) of the
+        columns in double (single rank), "equal" = 1, or an array like
+        `regions`.  write_grids=False (only with regions) skips the LDASOUT
+        grids, their copy and their file.  Without regions nothing changes."""
+        if not write_grids and regions is None:
+            raise ValueError("write_grids=False needs regions: the run would write nothing")
         if cosz not in ("device", "host"):
             raise ValueError(f"cosz must be 'device' or 'host', not {cosz!r}")
         self.cfg = cfg
@@ -294,6 +337,32 @@ class OfflineDriver:
             if self.gather.n_local != self.cs.ncol:
                 raise ValueError(f"rank {dist.get_rank()} holds {self.cs.ncol} columns, its "
                                  f"shard_range block of {total} has {self.gather.n_local}")
+        self.write_grids = bool(write_grids)
+        self.region_plan = None
+        self.regions_written = []
+        if regions is not None and (not dist.is_initialized() or dist.get_rank() == 0):
+            ids = np.asarray(regions)
+            if ids.shape != (total,):
+                raise ValueError(f"regions must hold one id per column ({total}), not {ids.shape}")
+            if isinstance(region_weights, str):
+                if region_weights == "equal":
+                    w = np.ones(total, np.float64)
+                elif region_weights == "area" and total == cols.n:
+                    w = area_weights(cols.static_f[L.STATIC_F.index("LAT")])
+                elif region_weights == "area":
+                    raise ValueError("region_weights='area' under a process group needs the "
+                                     "global columns' weights as an array")
+                else:
+                    raise ValueError("region_weights must be 'area', 'equal' or an array, not "
+                                     f"{region_weights!r}")
+            else:
+                w = np.asarray(region_weights, np.float64)
+            self.region_plan = RegionPlan.from_ids(ids, w).to(self.dev)
+            # sums and means of an output step, and their pinned staging buffers
+            self._reg_dev = torch.zeros((2, nout, self.region_plan.nreg), dtype=torch.float64,
+                                        device=self.dev)
+            self._reg_host = [torch.empty((2, nout, self.region_plan.nreg), dtype=torch.float64,
+                                          pin_memory=True) for _ in range(self.OUT_BUFFERS)]
         self.n_out = 0
         self.written = []
         self._writer = None
@@ -302,7 +371,9 @@ class OfflineDriver:
             # the output staging buffers up front: a page-locked allocation of
             # the whole set's fluxes costs tens of ms inside the time loop (the
             # file's grids in its byte order when the run has a grid)
-            if grid is not None:
+            if not self.write_grids:
+                self._writer_init(None)
+            elif grid is not None:
                 self._writer_init((nout, grid.shape[0] * grid.shape[1]),
                                   torch.int32 if self.dtype == torch.float32 else torch.int64)
             else:
@@ -322,7 +393,10 @@ class OfflineDriver:
         applied when columns are read from the files and undone when they are
         written, so files always hold the grid.
         host_threads: threads that build each step's forcing on the host
-        (ncio.LdasinForcing; default NMP_HOST_THREADS, else 8)."""
+        (ncio.LdasinForcing; default NMP_HOST_THREADS, else 8).
+        regions (in **kw): the path of a region file on the run's grid (int
+        REGION, optional double AREA; region_columns); region_weights "area"
+        then uses AREA if the file has it, else cos(latitude)."""
         P = params or Params.builtin()
         grid, sf, si = ncio.read_static(cfg.constfile, P.as_dict(), cfg.begdatetime)
         st, isn, t0, step = ncio.read_state(init or cfg.initfile, grid)
@@ -336,6 +410,11 @@ class OfflineDriver:
                                *([None] * 6))
         forcing = ncio.LdasinForcing(cfg.indir, grid, cfg.begdatetime, cfg.input_interval,
                                      cols=idx, threads=host_threads)
+        if kw.get("regions") is not None:
+            # the whole (ordered) column set's ids and weights: rank 0 reduces
+            # the gathered block
+            kw["regions"], kw["region_weights"] = region_columns(
+                os.fspath(kw["regions"]), grid, perm, kw.get("region_weights", "area"))
         drv = cls(cfg, cols, device, P, forcing, grid=grid, **kw)
         drv.t, drv.step_index = t0, step
         drv.perm, drv.cols_index = perm, idx
@@ -569,7 +648,8 @@ class OfflineDriver:
                     freed = self._write_output(d, path, t1, ost)
                     if self.gather is None:
                         self._diag_free = freed
-                    self.written.append(path)
+                    if self.write_grids:
+                        self.written.append(path)
             self.phase_s["output"] += time.perf_counter() - tp
             if _is_boundary(t1, cfg.begdatetime, res_every) and self.write:
                 os.makedirs(cfg.resdir, exist_ok=True)
@@ -644,10 +724,16 @@ class OfflineDriver:
         the header and the bytes (ncio.write_ldasout_grids) while the loop
         goes on stepping.  A buffer is reused once its previous file is
         written.  The device work goes on `stream` (default: the current
-        one); returns the event after which `d` has been read."""
+        one); returns the event after which `d` has been read.
+        With regions the block is also reduced to the regions' sums and means
+        on `stream` (nmp_region_reduce), which go to a small pinned buffer of
+        the same slot; the same writer job writes the REGIONS file.  The event
+        covers the reduce.  write_grids=False leaves only that."""
         stream = stream or torch.cuda.current_stream(self.dev)
         src = d
-        if self.grid is not None:
+        if not self.write_grids:
+            src = None
+        elif self.grid is not None:
             if self._out_point is None:
                 perm = getattr(self, "perm", None)
                 idx = np.asarray(self.grid.index)
@@ -661,21 +747,35 @@ class OfflineDriver:
                                      stream=stream)
             src = self._out_dev
         if self._writer is None:
-            self._writer_init(tuple(src.shape), src.dtype)
+            self._writer_init(None if src is None else tuple(src.shape),
+                              None if src is None else src.dtype)
         k = self._n_out_w % len(self._out_host)
         self._n_out_w += 1
         if self._out_fut[k] is not None:
             self._out_fut[k].result()
         h = self._out_host[k]
-        if h is None or h.shape != src.shape or h.dtype != src.dtype:
+        if src is not None and (h is None or h.shape != src.shape or h.dtype != src.dtype):
             h = self._out_host[k] = torch.empty(src.shape, dtype=src.dtype, pin_memory=True)
+        plan, rh, rpath = self.region_plan, None, None
+        if plan is not None:
+            rh, rpath = self._reg_host[k], ncio.regions_path(self.cfg.outdir, t1)
+            self.engine.region_reduce(d, plan, self._reg_dev[0], self._reg_dev[1], stream=stream)
+            self.regions_written.append(rpath)
         with torch.cuda.stream(stream):
-            h.copy_(src, non_blocking=True)
+            if src is not None:
+                h.copy_(src, non_blocking=True)
+            if rh is not None:
+                rh.copy_(self._reg_dev, non_blocking=True)
             ev = torch.cuda.Event()
             ev.record(stream)
 
         def job():
             ev.synchronize()
+            if rh is not None:
+                ncio.write_regions(rpath, plan.region_id, plan.ncolumns, plan.wsum,
+                                   rh.numpy()[1], t1, self.out_names)
+            if src is None:
+                return
             a = h.numpy()
             if self.grid is not None:
                 ncio.write_ldasout_grids(path, self.grid,
@@ -695,7 +795,9 @@ class OfflineDriver:
         from concurrent.futures import ThreadPoolExecutor
         self._writer = ThreadPoolExecutor(self.OUT_WRITERS)
         dtype = dtype or self.dtype
-        self._out_host = [torch.empty(shape, dtype=dtype, pin_memory=True)
+        # (shape None: a regions-only run stages no grids)
+        self._out_host = [None if shape is None else
+                          torch.empty(shape, dtype=dtype, pin_memory=True)
                           for _ in range(self.OUT_BUFFERS)]
         self._out_fut, self._n_out_w = [None] * self.OUT_BUFFERS, 0
 

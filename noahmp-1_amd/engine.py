@@ -355,6 +355,33 @@ class Engine:
                                               _ptr(out, lo), C.c_void_p(s.cuda_stream)),
                    "nmp_accum_finish")
 
+    # ---- region-aggregated output (nmp_region_reduce) ---------------------------
+    def region_reduce(self, fields: torch.Tensor, plan, sums: torch.Tensor,
+                      means: torch.Tensor | None = None, stream=None):
+        """nmp_region_reduce: sums[f, r] (and means[f, r] = sums / plan.wsum)
+        of the (nfield, n) block `fields` (engine precision) over the columns
+        of each region of `plan` (regions.RegionPlan on this device, built for
+        n columns), float64 (nfield, nreg), by the plan's fixed summation
+        tree; enqueued on `stream`.  The pass-1 scratch lives with the plan, so
+        calls that share a plan must be ordered by their streams."""
+        assert fields.dim() == 2, tuple(fields.shape)
+        nf, n = int(fields.shape[0]), int(fields.shape[1])
+        assert plan.dev is not None and plan.ncol == n, "plan.to(device) for this block"
+        self._check_block(fields, (nf, n), self.dtype, "fields")
+        self._check_block(sums, (nf, plan.nreg), torch.float64, "sums")
+        if means is not None:
+            self._check_block(means, (nf, plan.nreg), torch.float64, "means")
+        d = plan.dev
+        self._check_block(d["entry_col"], (plan.nchunk * L.REGION_CHUNK,), torch.int32, "entry_col")
+        self._check_block(d["entry_w"], (plan.nchunk * L.REGION_CHUNK,), torch.float64, "entry_w")
+        self._check_block(d["region_chunk0"], (plan.nreg + 1,), torch.int64, "region_chunk0")
+        self._check_block(d["wsum"], (plan.nreg,), torch.float64, "wsum")
+        s = stream if stream is not None else torch.cuda.current_stream(self.device)
+        _lib.check(self._lib.nmp_region_reduce(
+            self._h, n, n, nf, _ptr(fields), plan.nchunk, _ptr(d["entry_col"]), _ptr(d["entry_w"]),
+            plan.nreg, _ptr(d["region_chunk0"]), _ptr(d["wsum"]), _ptr(plan.partial(nf)),
+            _ptr(sums), _ptr(means), C.c_void_p(s.cuda_stream)), "nmp_region_reduce")
+
     # ---- the reference's other public routines (nmp_frh2o / nmp_calhum) ------
     def frh2o(self, sltyp, tkelv, smc, sh2o, status=None, stream=None):
         """frh2o (func.f90:4494-4598) elementwise.  Device tensors (engine

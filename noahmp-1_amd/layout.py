@@ -165,6 +165,8 @@ NCLIM = len(CLIMATE)
 NDIAG_FULL = len(DIAG_FULL)
 NDIAG_OUT = len(DIAG_OUT)
 assert NDIAG_FULL == 58 and NDIAG_OUT == 16
+# entries per chunk of a region plan (NMP_REGION_CHUNK, nmp_region_reduce)
+REGION_CHUNK = 256
 
 
 def s(name):

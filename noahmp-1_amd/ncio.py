@@ -26,7 +26,13 @@ scipy.io.netcdf_file (no netCDF-4/HDF5 library exists in this image):
   output fluxes on the grid, _FillValue off the land mask; an accumulating run
   (driver accumulate=True) appends its interval's 19 fields (layout.BUDGET) and
   stores the interval so far in its restart files (write_state accum,
-  read_accum).
+  read_accum);
+* REGIONS, one file per output time of a run with regions,
+  ``<YYYYMMDDHH>.REGIONS_DOMAIN1``: dimension `region`, region_id, ncolumns,
+  weight and one double variable per output field holding the regions'
+  weighted means (write_regions / read_regions / read_regions_series); the
+  region file such a run reads is an int REGION grid with an optional double
+  AREA (read_region_map).
 
 Columns are the grid's land points (LANDMASK == 1) in row-major order.
 """
@@ -635,3 +641,111 @@ def write_ldasout_grids(path: str, grid: Grid, grids_be: np.ndarray, t: datetime
 def read_ldasout(path: str, grid: Grid, names=L.DIAG_OUT) -> np.ndarray:
     raw = read_ldasin(path)
     return np.stack([grid.columns(raw[name]) for name in names])
+
+
+# ---- REGIONS (region-aggregated output) ------------------------------------------
+def regions_path(outdir: str, t: datetime.datetime) -> str:
+    return os.path.join(outdir, f"{stamp(t)}.REGIONS_DOMAIN1")
+
+
+def write_region_map(path: str, grid: Grid, region: np.ndarray, area: np.ndarray | None = None):
+    """A region file on the run's grid: int REGION(south_north, west_east)
+    (< 0: in no region) and, when given, double AREA (the points' weights)."""
+    ny, nx = grid.shape
+    f = netcdf_file(path, "w")
+    try:
+        f.createDimension("south_north", ny)
+        f.createDimension("west_east", nx)
+        dims = ("south_north", "west_east")
+        v = f.createVariable("REGION", "i4", dims)
+        v[:] = np.asarray(region, np.int32).reshape(ny, nx)
+        if area is not None:
+            v = f.createVariable("AREA", "f8", dims)
+            v[:] = np.asarray(area, np.float64).reshape(ny, nx)
+    finally:
+        f.close()
+
+
+def read_region_map(path: str, grid: Grid):
+    """(region (n,) int64, area (n,) float64 or None) of the grid's land points
+    (land-point order) from a region file on `grid`.  Points off the land mask
+    are no columns and so are in no region."""
+    f = _read(path)
+    try:
+        v = f.variables
+        if "REGION" not in v:
+            raise ValueError(f"{path}: no REGION variable")
+        reg = np.array(v["REGION"][:])
+        if reg.shape != grid.shape:
+            raise ValueError(f"{path}: REGION is {reg.shape}, the run's grid {grid.shape}")
+        if reg.dtype.kind not in "iu":
+            raise ValueError(f"{path}: REGION must be an integer variable, not {reg.dtype}")
+        area = None
+        if "AREA" in v:
+            area = grid.columns(np.array(v["AREA"][:], np.float64))
+        return grid.columns(reg).astype(np.int64), area
+    finally:
+        f.close()
+
+
+def write_regions(path: str, region_id, ncolumns, weight, means: np.ndarray,
+                  t: datetime.datetime, names=L.DIAG_OUT):
+    """One output time's region means: dimension `region`, region_id (int),
+    ncolumns (int), weight (double: the plan's wsum) and one double variable
+    per output field (`names`, the rows of means (nfield, nregion)) holding the
+    regions' weighted means; the LDASOUT file's valid_time attribute."""
+    means = np.asarray(means, np.float64)
+    nreg = int(np.asarray(region_id).size)
+    assert means.shape == (len(names), nreg), (means.shape, len(names), nreg)
+    f = netcdf_file(path, "w")
+    try:
+        f.createDimension("region", nreg)
+        f.valid_time = t.isoformat()
+        for name, kind, a in (("region_id", "i4", region_id), ("ncolumns", "i4", ncolumns),
+                              ("weight", "f8", weight)):
+            v = f.createVariable(name, kind, ("region",))
+            v[:] = np.asarray(a).astype(kind)
+        for name, row in zip(names, means):
+            v = f.createVariable(name, "f8", ("region",))
+            v[:] = row
+    finally:
+        f.close()
+
+
+_REGION_META = ("region_id", "ncolumns", "weight")
+
+
+def read_regions(path: str) -> dict:
+    """A REGIONS file: region_id, ncolumns, weight, names (the fields in file
+    order), means (nfield, nregion) float64 and time."""
+    f = _read(path)
+    try:
+        names = [k for k in f.variables if k not in _REGION_META]
+        vt = f.valid_time.decode() if isinstance(f.valid_time, bytes) else f.valid_time
+        nreg = f.dimensions["region"]
+        out = {k: np.array(f.variables[k][:]).astype(np.float64 if k == "weight" else np.int64)
+               for k in _REGION_META}
+        out["names"] = names
+        out["means"] = (np.stack([np.array(f.variables[k][:], np.float64) for k in names])
+                        if names else np.zeros((0, nreg)))
+        out["time"] = datetime.datetime.fromisoformat(vt)
+        return out
+    finally:
+        f.close()
+
+
+def read_regions_series(outdir: str) -> dict:
+    """A run's REGIONS files stacked in time order: times (list), names,
+    region_id, ncolumns, weight and means (time, field, region)."""
+    import glob
+    files = sorted(glob.glob(os.path.join(outdir, "*.REGIONS_DOMAIN1")))
+    if not files:
+        raise FileNotFoundError(os.path.join(outdir, "*.REGIONS_DOMAIN1"))
+    recs = sorted((read_regions(p) for p in files), key=lambda r: r["time"])
+    first = recs[0]
+    for r in recs[1:]:
+        if r["names"] != first["names"] or not np.array_equal(r["region_id"], first["region_id"]):
+            raise ValueError(f"{outdir}: the REGIONS files do not share fields and regions")
+    return dict(times=[r["time"] for r in recs], names=first["names"],
+                region_id=first["region_id"], ncolumns=first["ncolumns"],
+                weight=first["weight"], means=np.stack([r["means"] for r in recs]))

@@ -3,6 +3,8 @@
 
     python noahmp_offline.py [case.nml] [--ncol N] [--kind casenml|mixed|conus]
                              [--device D] [--restart FILE] [--accumulate]
+                             [--regions FILE [--region-weights area|equal]
+                              [--regions-only]]
 
 Reads the namelist like the reference (noahmp_amd.config.Config ==
 offline/noahmp_config.Config) and then does what the reference driver does
@@ -55,15 +57,33 @@ def main(argv=None):
                          "of the energy fluxes, totals of the water fluxes (ACCPRCP, ACCECAN, "
                          "..., SFCRNOFF, UGDRNOFF) and the water budget's closure (DSTOR, "
                          "WBRES) -- 35 fields per LDASOUT file instead of 16")
+    ap.add_argument("--regions", default=None, metavar="FILE",
+                    help="netCDF cases: a region file on the run's grid (int REGION, optional "
+                         "double AREA); every output time then also writes the regions' "
+                         "weighted means of the output fields (<stamp>.REGIONS_DOMAIN1)")
+    ap.add_argument("--region-weights", default="area", choices=("area", "equal"),
+                    help="weights of the region means: the file's AREA (else cos(latitude)), "
+                         "or 1 for every column")
+    ap.add_argument("--regions-only", action="store_true",
+                    help="with --regions: write the REGIONS files and no LDASOUT grids")
     a = ap.parse_args(argv)
+    if a.regions_only and not a.regions:
+        ap.error("--regions-only needs --regions")
     cfg = config.Config(a.nmlfile)
     P = Params.builtin()
     if os.path.isfile(cfg.constfile):
+        rkw = {}
+        if a.regions:
+            rkw = dict(regions=a.regions, region_weights=a.region_weights,
+                       write_grids=not a.regions_only)
         drv = driver.OfflineDriver.from_files(cfg, device=a.device, params=P, init=a.restart,
                                               precision=a.precision, cosz=a.cosz,
-                                              ingest=not a.no_ingest, accumulate=a.accumulate)
+                                              ingest=not a.no_ingest, accumulate=a.accumulate,
+                                              **rkw)
         a.ncol = drv.cs.ncol
     else:
+        if a.regions:
+            ap.error("--regions needs a run from files (the namelist's static_parameter_file)")
         cols = cases.make_columns(a.ncol, a.kind, P.as_dict(), seed=0,
                                   julian=timeman.julian(cfg.begdatetime))
         drv = driver.OfflineDriver(cfg, cols, device=a.device, params=P,
@@ -75,7 +95,8 @@ def main(argv=None):
     drv.run()
     el = time.perf_counter() - t0
     print(f"{drv.step_index} steps x {a.ncol} columns to {drv.t.isoformat()} in {el:.2f} s; "
-          f"{len(drv.written)} output files in {cfg.outdir}; status bits set on "
+          f"{len(drv.written) + len(drv.regions_written)} output files in {cfg.outdir}; "
+          "status bits set on "
           f"{int((drv.cs.status != 0).sum())} columns")
     return 0
 
