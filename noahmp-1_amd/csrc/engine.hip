@@ -410,6 +410,32 @@ int nmp_ldasin_ingest(nmp_engine* eng, int64_t ncol, int64_t ld, int64_t npts,
              : NMP_E_DEVICE;
 }
 
+int nmp_ldasin_regrid(nmp_engine* eng, int64_t ncol, int64_t ld, int64_t npts,
+                      const void* grid_be, const int32_t* corner, const double* weight,
+                      uint32_t nearest_mask, float* ldasin, void* stream) {
+  if (!eng || ncol < 0 || ld < ncol || ld >= kMaxColumns || npts < 1 || npts >= kMaxColumns)
+    return NMP_E_ARG;
+  if (ncol == 0) return NMP_OK;
+  if (!grid_be || !corner || !weight || !ldasin) return NMP_E_ARG;
+  if (ensure_device(eng->device) != NMP_OK) return NMP_E_DEVICE;
+  return nmp::launch_ldasin_regrid(ncol, ld, npts, grid_be, corner, weight, nearest_mask, ldasin,
+                                   static_cast<hipStream_t>(stream)) == hipSuccess
+             ? NMP_OK
+             : NMP_E_DEVICE;
+}
+
+int nmp_ldasin_downscale(nmp_engine* eng, int64_t ncol, int64_t ld, const float* dz, double lapse,
+                         float* ldasin, void* stream) {
+  if (!eng || ncol < 0 || ld < ncol || ld >= kMaxColumns) return NMP_E_ARG;
+  if (ncol == 0) return NMP_OK;
+  if (!dz || !ldasin) return NMP_E_ARG;
+  if (ensure_device(eng->device) != NMP_OK) return NMP_E_DEVICE;
+  return nmp::launch_ldasin_downscale(ncol, ld, dz, lapse, ldasin,
+                                      static_cast<hipStream_t>(stream)) == hipSuccess
+             ? NMP_OK
+             : NMP_E_DEVICE;
+}
+
 int nmp_ldasout_grid(nmp_engine* eng, int64_t ncol, int64_t ld, int64_t npts, int nfield,
                      const void* diag, const int32_t* point, double fill, void* grid_be,
                      void* stream) {

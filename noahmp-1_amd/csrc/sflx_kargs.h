@@ -70,6 +70,15 @@ hipError_t launch_ldasout_grid(int precision, int64_t ncol, int64_t ld, int64_t 
                                const void* diag, const int32_t* point, double fill, void* grid_be,
                                hipStream_t stream);
 
+// csrc/regrid.hip: an LDASIN file on its own (coarse) grid -> the block's 8
+// rows by four weighted source entries per column, and the block's elevation
+// (lapse-rate) correction in place
+hipError_t launch_ldasin_regrid(int64_t ncol, int64_t ld, int64_t npts, const void* grid_be,
+                                const int32_t* corner, const double* weight,
+                                uint32_t nearest_mask, float* block, hipStream_t stream);
+hipError_t launch_ldasin_downscale(int64_t ncol, int64_t ld, const float* dz, double lapse,
+                                   float* block, hipStream_t stream);
+
 // csrc/accum.hip: accumulated output over an output interval -- the step's
 // fluxes x dt into the double accumulators, the column water storage, and the
 // interval's means / totals / budget residual (which also starts the next one)

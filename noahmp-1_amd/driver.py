@@ -43,7 +43,10 @@ the block in its column order (nmp_ldasin_ingest) on the upload stream,
 beside the steps of the previous file; the block stays resident while each
 range forms the 12 forcing fields, COSZ included, on its own stream right
 before its launch (nmp_forcing_from_ldasin_geo), waiting only on that
-block's event.  ingest=False builds the block on the host
+block's event.  Files on a coarser grid of their own (from_files
+forcing_grid) take the same path with nmp_ldasin_regrid in nmp_ldasin_ingest's
+place, and downscale=True adds nmp_ldasin_downscale on the upload stream
+before the block's event.  ingest=False builds the block on the host
 (ncio.LdasinForcing.block); cosz="host" uploads the variables plus the
 host's COSZ every step (ncio.LdasinForcing.raw, nmp_forcing_from_ldasin);
 the 12-field host form (48 B per column, 96 in fp64) remains for providers
@@ -226,7 +229,8 @@ class OfflineDriver:
                  math: str = "ref", zsoil=cases.CASE_NML_ZSOIL, write: bool = True,
                  streams: int = 2, grid: ncio.Grid | None = None, ldasin_upload: bool = True,
                  cosz: str = "device", ingest: bool = True, accumulate: bool = False,
-                 regions=None, region_weights="area", write_grids: bool = True):
+                 regions=None, region_weights="area", write_grids: bool = True,
+                 downscale: bool = False, lapse_rate: float = 0.0065):
         """cols: this rank's columns (all of them on a single rank); under an
         initialised process group they must be the rank's shard_range block of
         the global column set.  ldasin_upload: with a provider that has
@@ -256,11 +260,25 @@ class OfflineDriver:
         (nmp_region_reduce).  region_weights: "area" = cos(latitude) of the
         columns in double (single rank), "equal" = 1, or an array like
         `regions`.  write_grids=False (only with regions) skips the LDASOUT
-        grids, their copy and their file.  Without regions nothing changes."""
+        grids, their copy and their file.  Without regions nothing changes.
+        downscale: with a provider whose files lie on their own grid
+        (ncio.LdasinForcing(src=...) with HGT and HGT_M), correct every
+        resident LDASIN block on the device for the elevation difference
+        between the model terrain and the source grid (nmp_ldasin_downscale,
+        lapse_rate in K/m), on the upload stream right after the block is
+        formed there or uploaded; needs ldasin_upload and cosz="device"."""
         if not write_grids and regions is None:
             raise ValueError("write_grids=False needs regions: the run would write nothing")
         if cosz not in ("device", "host"):
             raise ValueError(f"cosz must be 'device' or 'host', not {cosz!r}")
+        dz_host = None
+        if downscale:  # (refused before any device work)
+            if not (ldasin_upload and cosz == "device" and hasattr(forcing, "raw")):
+                raise ValueError("downscale needs LDASIN files uploaded as resident blocks "
+                                 "(ldasin_upload=True, cosz='device')")
+            if not hasattr(forcing, "dz"):
+                raise ValueError("downscale needs LDASIN files on a forcing grid")
+            dz_host = forcing.dz()  # ValueError without HGT and HGT_M
         self.cfg = cfg
         self.grid = grid
         self.engine = Engine(params or Params.builtin(), cfg.engine_options(), device, precision,
@@ -316,6 +334,9 @@ class OfflineDriver:
             self.raw_fbuf = torch.empty((2, L.NFORCING, self.cs.ncol), dtype=self.dtype,
                                         device=self.dev)
         self.geo, self._blocks = None, {}
+        self.downscale, self.lapse_rate, self.dz = bool(downscale), float(lapse_rate), None
+        if self.downscale:
+            self.dz = torch.as_tensor(dz_host, device=self.dev).contiguous()
         self._prefetch, self._prefetch_pool = None, None
         # single-rank output: grids and copies on a stream of their own, so the
         # next steps need not wait for them (only the next output step waits
@@ -323,13 +344,20 @@ class OfflineDriver:
         self.out_stream, self._diag_free = None, None
         if self.raw_upload is not None and cosz == "device":
             self.geo = torch.as_tensor(self.forcing.geo(), device=self.dev).contiguous()
-        self.ingest = None
+        self.ingest, self.point, self.regrid_plan = None, None, None
         if self.geo is not None and ingest and hasattr(self.forcing, "grid_raw"):
-            npts = self.forcing.grid.shape[0] * self.forcing.grid.shape[1]
+            # (files on their own grid: the source grid's points, and the
+            # columns' regrid plan instead of a point each)
+            plan = getattr(self.forcing, "plan", None)
+            npts = self.forcing.grid.shape[0] * self.forcing.grid.shape[1] if plan is None \
+                else plan.npts
             self.ingest = ForcingUpload(npts, torch.int32, self.dev, nfield=L.NLDASIN - 1)
             self.ingest_blk = torch.zeros((2, L.NLDASIN, self.cs.ncol), dtype=torch.float32,
                                           device=self.dev)
-            self.point = torch.as_tensor(self.forcing.point(), device=self.dev)
+            if plan is None:
+                self.point = torch.as_tensor(self.forcing.point(), device=self.dev)
+            else:
+                self.regrid_plan = plan.to(self.dev)
         self.phase_s = defaultdict(float)
         self.gather = None
         if dist.is_initialized():
@@ -383,10 +411,18 @@ class OfflineDriver:
     @classmethod
     def from_files(cls, cfg: Config, device: int = 0, params: Params | None = None,
                    init: str | None = None, order: str | None = "lon-snow-type",
-                   host_threads: int | None = None, **kw) -> "OfflineDriver":
+                   host_threads: int | None = None, forcing_grid: str | None = None,
+                   nearest=(), **kw) -> "OfflineDriver":
         """The run the namelist describes: static file (cfg.constfile), initial
         state (cfg.initfile, or `init`) and LDASIN forcing (cfg.indir every
         cfg.input_frequency), netCDF-3 files in the layouts of ncio.py.
+        forcing_grid: the path of a forcing-grid file (ncio.read_forcing_grid):
+        the LDASIN files are stored on that coarser rectilinear grid and are
+        interpolated to the columns (bilinear; the variables named in `nearest`
+        take their nearest source point) -- on the device from the files'
+        bytes (nmp_ldasin_regrid) where a model-grid file would be ingested,
+        else on the host, the same bits.  downscale, lapse_rate: see __init__;
+        dz = the file's HGT_M at the column minus its HGT interpolated to it.
 
         order: the land points are laid out in the engine in this coherent
         order (order.coherent_order; None = grid order).  The permutation is
@@ -408,8 +444,13 @@ class OfflineDriver:
             idx = perm[s0:s0 + cnt]
         cols = cases.ColumnSet(sf[:, idx], si[:, idx], st[:, idx], isn[idx], grid.lon_rad[idx],
                                *([None] * 6))
+        fkw = {}
+        if forcing_grid is not None:
+            fkw = dict(src=ncio.read_forcing_grid(os.fspath(forcing_grid)), nearest=nearest)
+        elif kw.get("downscale") or nearest:
+            raise ValueError("downscale and nearest need forcing_grid")
         forcing = ncio.LdasinForcing(cfg.indir, grid, cfg.begdatetime, cfg.input_interval,
-                                     cols=idx, threads=host_threads)
+                                     cols=idx, threads=host_threads, **fkw)
         if kw.get("regions") is not None:
             # the whole (ordered) column set's ids and weights: rank 0 reduces
             # the gathered block
@@ -592,6 +633,9 @@ class OfflineDriver:
                     cols=rng)
                 after, upload = cur, None
             elif info is not None:  # LDASIN files, the 12-field form: built into the pinned buffer
+                if self.downscale:
+                    raise ValueError(f"downscale: the input file of {t0.isoformat()} carries its "
+                                     "own CO2AIR / O2AIR and takes the 12-field host form")
                 step_k, t_k = self.step_index, t0
                 f = self.upload.put(fill=lambda h: self.forcing(step_k, t_k, out=h))
             else:
@@ -666,11 +710,16 @@ class OfflineDriver:
         """Upload the LDASIN block of t's input file once; returns the device
         block and the ForcingUpload whose stream and slot guard it.  With
         `ingest` (and no COSZ in the file) the file's bytes go up as stored and
-        the engine forms the block's rows (nmp_ldasin_ingest on the upload's
-        stream); otherwise the host builds the block (ncio block)."""
+        the engine forms the block's rows (nmp_ldasin_ingest, or
+        nmp_ldasin_regrid for files on their own grid, on the upload's stream);
+        otherwise the host builds the block (ncio block).  With downscale either
+        block is then corrected for elevation on the same stream
+        (nmp_ldasin_downscale), before its event."""
         if self.ingest is None or file_cosz or not self.forcing.ingestible(t):
             up = self.raw_upload
             blk = up.put(fill=lambda h: self.forcing.block(t, out=h))
+            if self.downscale:
+                self.engine.ldasin_downscale(blk, self.dz, self.lapse_rate, stream=up.stream)
             ev = torch.cuda.Event()
             ev.record(up.stream)
             return blk, ev, up, up.last_slot
@@ -682,7 +731,13 @@ class OfflineDriver:
         self._prefetch = None
         g = up.put(fill=lambda h: self.forcing.grid_raw(t, out=h), prefilled=ready)
         blk = self.ingest_blk[up.last_slot]
-        self.engine.ldasin_ingest(g, self.point, blk, stream=up.stream)
+        if self.regrid_plan is not None:
+            self.engine.ldasin_regrid(g, self.regrid_plan, blk, self.forcing.nearest_mask,
+                                      stream=up.stream)
+        else:
+            self.engine.ldasin_ingest(g, self.point, blk, stream=up.stream)
+        if self.downscale:
+            self.engine.ldasin_downscale(blk, self.dz, self.lapse_rate, stream=up.stream)
         # read the next input file's bytes ahead (a missing or non-fp32 file
         # fails only the prefetch; its step then takes the plain path)
         nxt = ti + self.forcing.every

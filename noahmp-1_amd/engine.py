@@ -268,6 +268,45 @@ class Engine:
                                                _ptr(grid_be, 0), _ptr(point, 0), _ptr(out, 0),
                                                C.c_void_p(s.cuda_stream)), "nmp_ldasin_ingest")
 
+    def ldasin_regrid(self, grid_be: torch.Tensor, plan, out: torch.Tensor,
+                      nearest_mask: int = 0, stream=None):
+        """nmp_ldasin_regrid: rows T2D..LWDOWN of the (NLDASIN, n) fp32 block
+        `out` from an LDASIN file stored on its own (coarse) grid: grid_be =
+        (8, npts) 4-byte words, the file's big-endian fp32 grids in
+        layout.LDASIN order; `plan` (regrid.RegridPlan on this device, built
+        for n columns and npts source points) gives each column its four
+        weighted source entries.  Bit v of nearest_mask: variable v takes its
+        nearest entry (regrid.nearest_mask).  The COSZ row is left as it is."""
+        n = int(out.shape[1])
+        assert grid_be.dim() == 2 and grid_be.shape[0] == L.NLDASIN - 1
+        assert grid_be.element_size() == 4 and grid_be.is_contiguous()
+        assert plan.dev is not None and plan.ncol == n, "plan.to(device) for this block"
+        assert plan.npts == int(grid_be.shape[1]), (plan.npts, tuple(grid_be.shape))
+        corner, weight = plan.dev["corner"], plan.dev["weight"]
+        self._check_block(corner, (4, n), torch.int32, "corner")
+        self._check_block(weight, (4, n), torch.float64, "weight")
+        self._check_block(out, (L.NLDASIN, n), torch.float32, "out")
+        assert grid_be.device.type == "cuda" and grid_be.device.index == self.device
+        assert 0 <= int(nearest_mask) < (1 << (L.NLDASIN - 1))
+        s = stream if stream is not None else torch.cuda.current_stream(self.device)
+        _lib.check(self._lib.nmp_ldasin_regrid(self._h, n, n, plan.npts, _ptr(grid_be, 0),
+                                               _ptr(corner), _ptr(weight), int(nearest_mask),
+                                               _ptr(out, 0), C.c_void_p(s.cuda_stream)),
+                   "nmp_ldasin_regrid")
+
+    def ldasin_downscale(self, block: torch.Tensor, dz: torch.Tensor, lapse: float, stream=None):
+        """nmp_ldasin_downscale: rows T2D, Q2D, PSFC and LWDOWN of the
+        (NLDASIN, n) fp32 block corrected in place for the elevation
+        difference dz (n,) fp32 (model minus source, m) with the lapse rate
+        `lapse` (K/m); the other rows are untouched."""
+        n = int(block.shape[1])
+        self._check_block(block, (L.NLDASIN, n), torch.float32, "block")
+        self._check_block(dz, (n,), torch.float32, "dz")
+        s = stream if stream is not None else torch.cuda.current_stream(self.device)
+        _lib.check(self._lib.nmp_ldasin_downscale(self._h, n, n, _ptr(dz, 0), float(lapse),
+                                                  _ptr(block, 0), C.c_void_p(s.cuda_stream)),
+                   "nmp_ldasin_downscale")
+
     def ldasout_grid(self, diag: torch.Tensor, point: torch.Tensor, out: torch.Tensor,
                      fill: float, stream=None):
         """nmp_ldasout_grid: the (nfield, n) diagnostics `diag` (engine

@@ -32,7 +32,14 @@ scipy.io.netcdf_file (no netCDF-4/HDF5 library exists in this image):
   weight and one double variable per output field holding the regions'
   weighted means (write_regions / read_regions / read_regions_series); the
   region file such a run reads is an int REGION grid with an optional double
-  AREA (read_region_map).
+  AREA (read_region_map);
+* forcing-grid file, for LDASIN files stored on a coarser rectilinear grid of
+  their own (LdasinForcing(src=...), driver forcing_grid): double
+  lat(src_south_north) and lon(src_west_east), optionally double HGT (the
+  source's elevation) and int MASK (1 = valid) on (src_south_north,
+  src_west_east) and double HGT_M(south_north, west_east), the model terrain
+  (write_forcing_grid / read_forcing_grid).  The LDASIN files then carry their
+  variables on (Time, src_south_north, src_west_east)-shaped grids.
 
 Columns are the grid's land points (LANDMASK == 1) in row-major order.
 """
@@ -277,6 +284,81 @@ def read_accum(path: str, grid: Grid):
         f.close()
 
 
+# ---- forcing grid (LDASIN files on their own, coarser grid) -----------------------
+class ForcingGrid:
+    """The rectilinear grid a run's LDASIN files are stored on when it is not
+    the model grid: lat (ny,) and lon (nx,) degrees, and optionally hgt
+    (ny, nx) the source's elevation in m, mask (ny, nx) bool (true = a valid
+    source point) and hgt_m, the model terrain on the run's own grid."""
+
+    def __init__(self, lat, lon, hgt=None, mask=None, hgt_m=None):
+        self.lat = np.asarray(lat, np.float64)
+        self.lon = np.asarray(lon, np.float64)
+        self.shape = (int(self.lat.size), int(self.lon.size))
+        self.hgt = None if hgt is None else np.asarray(hgt, np.float64).reshape(self.shape)
+        self.mask = None if mask is None else np.asarray(mask).reshape(self.shape) == 1
+        self.hgt_m = None if hgt_m is None else np.asarray(hgt_m, np.float64)
+
+    @property
+    def npts(self) -> int:
+        return self.shape[0] * self.shape[1]
+
+    def as_grid(self) -> Grid:
+        """The source points as a Grid (every point a 'land point'), for
+        write_ldasin of a file on this grid."""
+        lat = self.lat[:, None] + 0.0 * self.lon[None, :]
+        lon = self.lon[None, :] + 0.0 * self.lat[:, None]
+        return Grid(lat, lon, np.ones(self.shape, bool))
+
+
+def write_forcing_grid(path: str, fg: ForcingGrid):
+    """A forcing-grid file: double lat(src_south_north), lon(src_west_east),
+    optional double HGT and int MASK (1 = valid) on (src_south_north,
+    src_west_east), optional double HGT_M(south_north, west_east)."""
+    f = netcdf_file(path, "w")
+    try:
+        f.createDimension("src_south_north", fg.shape[0])
+        f.createDimension("src_west_east", fg.shape[1])
+        v = f.createVariable("lat", "f8", ("src_south_north",))
+        v[:] = fg.lat
+        v.units = "degrees_north"
+        v = f.createVariable("lon", "f8", ("src_west_east",))
+        v[:] = fg.lon
+        v.units = "degrees_east"
+        dims = ("src_south_north", "src_west_east")
+        if fg.hgt is not None:
+            v = f.createVariable("HGT", "f8", dims)
+            v[:] = fg.hgt
+            v.units = "m"
+        if fg.mask is not None:
+            v = f.createVariable("MASK", "i4", dims)
+            v[:] = fg.mask.astype(np.int32)
+        if fg.hgt_m is not None:
+            if fg.hgt_m.ndim != 2:
+                raise ValueError("hgt_m must be on the run's (south_north, west_east) grid")
+            f.createDimension("south_north", fg.hgt_m.shape[0])
+            f.createDimension("west_east", fg.hgt_m.shape[1])
+            v = f.createVariable("HGT_M", "f8", ("south_north", "west_east"))
+            v[:] = fg.hgt_m
+            v.units = "m"
+    finally:
+        f.close()
+
+
+def read_forcing_grid(path: str) -> ForcingGrid:
+    f = _read(path)
+    try:
+        v = f.variables
+        for k in ("lat", "lon"):
+            if k not in v:
+                raise ValueError(f"{path}: no {k} variable")
+        opt = lambda k: np.array(v[k][:]) if k in v else None  # noqa: E731
+        return ForcingGrid(np.array(v["lat"][:]), np.array(v["lon"][:]), opt("HGT"), opt("MASK"),
+                           opt("HGT_M"))
+    finally:
+        f.close()
+
+
 # ---- LDASIN ---------------------------------------------------------------------
 def write_ldasin(path: str, grid: Grid, forcing: np.ndarray, t: datetime.datetime,
                  extras=True):
@@ -329,12 +411,31 @@ class LdasinForcing:
     COSZ, a double cosine per column and step, dominated the host's time."""
 
     def __init__(self, indir: str, grid: Grid, begin: datetime.datetime,
-                 every: datetime.timedelta, cols: slice | None = None, threads: int | None = None):
+                 every: datetime.timedelta, cols: slice | None = None, threads: int | None = None,
+                 src: "ForcingGrid | None" = None, nearest=()):
         """cols: the land points this rank steps, in engine order (a slice or an
         index array; default: all of them in grid order).  threads: host
-        threads (default NMP_HOST_THREADS, else 8)."""
+        threads (default NMP_HOST_THREADS, else 8).
+        src: the files are stored on this ForcingGrid instead of the model
+        grid; every variable is then interpolated to this rank's columns by
+        their bilinear plan (regrid.RegridPlan, `plan`), on the host in _load
+        (apply_host) or on the device from grid_raw's bytes
+        (nmp_ldasin_regrid) -- the same bits.  nearest: the LDASIN variables
+        that take their nearest source point instead.  Without src every byte
+        and code path is as before."""
         self.indir, self.grid, self.begin, self.every = indir, grid, begin, every
         self.cols = cols if cols is not None else slice(0, grid.n)
+        self.src, self.plan, self.nearest_mask = src, None, 0
+        self.nearest = tuple(v if isinstance(v, str) else L.LDASIN[int(v)] for v in nearest)
+        # shape and size of the grid the files are stored on
+        self.file_shape = tuple(grid.shape) if src is None else tuple(src.shape)
+        self.npts = self.file_shape[0] * self.file_shape[1]
+        if src is not None:
+            from .regrid import RegridPlan, nearest_mask
+            self.nearest_mask = nearest_mask(self.nearest)
+            self.plan = RegridPlan.bilinear(src.lat, src.lon,
+                                            grid.columns(grid.lat_deg)[self.cols],
+                                            grid.columns(grid.lon_deg)[self.cols], src.mask)
         self._t, self._fields = None, None
         self.lat, self.lon = self.grid.lat_rad[self.cols], self.grid.lon_rad[self.cols]
         # the latitude factors of COSZ, once (timeman.cosz evaluates the same
@@ -370,6 +471,11 @@ class LdasinForcing:
             def one(k):
                 v = f.variables[k]
                 s = np.asarray(v[0] if v.dimensions[0] == "Time" else v[:]).reshape(-1)
+                if self.plan is not None:  # the source grid's values at the columns
+                    if s.dtype.kind != "f" or s.dtype.itemsize != 4:
+                        s = s.astype(np.float32)
+                    out[k] = self.plan.apply_host(s, nearest=k in self.nearest)
+                    return
                 out[k] = s[self._gidx].astype(s.dtype.newbyteorder("="))
             self._map(one, names)
         finally:
@@ -486,11 +592,11 @@ class LdasinForcing:
             try:
                 self._vars = frozenset(f.variables)
                 # the device ingest takes the 8 variables as fp32 grids
-                npts = self.grid.shape[0] * self.grid.shape[1]
+                npts = self.npts
                 self._ingestible = all(
                     k in f.variables and f.variables[k].data.dtype == np.dtype(">f4") and
                     f.variables[k].data.size in (npts, npts * f.variables[k].data.shape[0])
-                    and f.variables[k].data.shape[-2:] == self.grid.shape
+                    and f.variables[k].data.shape[-2:] == self.file_shape
                     for k in L.LDASIN[:-1])
             finally:
                 f.close()
@@ -502,14 +608,29 @@ class LdasinForcing:
 
     def ingestible(self, t: datetime.datetime) -> bool:
         """The input file of t holds the 8 LDASIN variables as fp32 grids of
-        the run's shape (what grid_raw / nmp_ldasin_ingest take)."""
+        the run's shape -- with `src`, of the source grid's (what grid_raw and
+        nmp_ldasin_ingest / nmp_ldasin_regrid take)."""
         self.variables(t)
         return self._ingestible
 
     def point(self) -> np.ndarray:
         """int32 (n,): the file grid point (row-major index) of each engine
-        column -- nmp_ldasin_ingest's `point`."""
+        column -- nmp_ldasin_ingest's `point`.  Files on their own grid
+        (`src`) have `plan` in its place."""
+        if self.plan is not None:
+            raise ValueError("files on their own grid have no point per column: use plan")
         return self._gidx.astype(np.int32)
+
+    def dz(self) -> np.ndarray:
+        """float32 (n,): the model terrain at each engine column minus the
+        source grid's elevation interpolated to it (plan.interp_scalar, in
+        double) -- nmp_ldasin_downscale's dz.  Needs HGT and HGT_M."""
+        if self.src is None or self.src.hgt is None or self.src.hgt_m is None:
+            raise ValueError("downscaling needs a forcing grid with HGT and HGT_M")
+        if tuple(self.src.hgt_m.shape) != tuple(self.grid.shape):
+            raise ValueError(f"HGT_M is {self.src.hgt_m.shape}, the run's grid {self.grid.shape}")
+        model = self.grid.columns(self.src.hgt_m)[self.cols]
+        return (model - self.plan.interp_scalar(self.src.hgt)).astype(np.float32)
 
     def grid_raw(self, t: datetime.datetime, out: np.ndarray | None = None):
         """The input file's 8 LDASIN variables (layout.LDASIN order, COSZ
@@ -521,7 +642,7 @@ class LdasinForcing:
         path = ldasin_path(self.indir, self.input_time(t))
         if not os.path.isfile(path):
             raise FileNotFoundError(path)
-        npts = self.grid.shape[0] * self.grid.shape[1]
+        npts = self.npts
         r = np.empty((L.NLDASIN - 1, npts), ">f4") if out is None else out
         assert r.shape == (L.NLDASIN - 1, npts) and r.dtype.itemsize == 4
         f = netcdf_file(path, "r", mmap=True)

@@ -5,6 +5,8 @@
                              [--device D] [--restart FILE] [--accumulate]
                              [--regions FILE [--region-weights area|equal]
                               [--regions-only]]
+                             [--forcing-grid FILE [--downscale] [--lapse-rate K_PER_M]
+                              [--nearest RAINRATE,SWDOWN]]
 
 Reads the namelist like the reference (noahmp_amd.config.Config ==
 offline/noahmp_config.Config) and then does what the reference driver does
@@ -66,9 +68,23 @@ def main(argv=None):
                          "or 1 for every column")
     ap.add_argument("--regions-only", action="store_true",
                     help="with --regions: write the REGIONS files and no LDASOUT grids")
+    ap.add_argument("--forcing-grid", default=None, metavar="FILE",
+                    help="netCDF cases: the LDASIN files are stored on the coarser rectilinear "
+                         "grid this file describes (lat, lon, optional HGT, MASK, HGT_M) and are "
+                         "interpolated to the model grid on the device (nmp_ldasin_regrid)")
+    ap.add_argument("--downscale", action="store_true",
+                    help="with --forcing-grid: correct T2D, PSFC, Q2D and LWDOWN for the "
+                         "elevation difference HGT_M - HGT (nmp_ldasin_downscale)")
+    ap.add_argument("--lapse-rate", type=float, default=0.0065, metavar="K_PER_M",
+                    help="lapse rate of --downscale (default 0.0065 K/m)")
+    ap.add_argument("--nearest", default="", metavar="VAR[,VAR]",
+                    help="with --forcing-grid: LDASIN variables that take their nearest source "
+                         "point instead of the bilinear value, e.g. RAINRATE,SWDOWN")
     a = ap.parse_args(argv)
     if a.regions_only and not a.regions:
         ap.error("--regions-only needs --regions")
+    if (a.downscale or a.nearest) and not a.forcing_grid:
+        ap.error("--downscale and --nearest need --forcing-grid")
     cfg = config.Config(a.nmlfile)
     P = Params.builtin()
     if os.path.isfile(cfg.constfile):
@@ -76,14 +92,19 @@ def main(argv=None):
         if a.regions:
             rkw = dict(regions=a.regions, region_weights=a.region_weights,
                        write_grids=not a.regions_only)
+        if a.forcing_grid:
+            rkw.update(forcing_grid=a.forcing_grid, downscale=a.downscale,
+                       lapse_rate=a.lapse_rate,
+                       nearest=tuple(v for v in a.nearest.split(",") if v))
         drv = driver.OfflineDriver.from_files(cfg, device=a.device, params=P, init=a.restart,
                                               precision=a.precision, cosz=a.cosz,
                                               ingest=not a.no_ingest, accumulate=a.accumulate,
                                               **rkw)
         a.ncol = drv.cs.ncol
     else:
-        if a.regions:
-            ap.error("--regions needs a run from files (the namelist's static_parameter_file)")
+        if a.regions or a.forcing_grid:
+            ap.error("--regions and --forcing-grid need a run from files (the namelist's "
+                     "static_parameter_file)")
         cols = cases.make_columns(a.ncol, a.kind, P.as_dict(), seed=0,
                                   julian=timeman.julian(cfg.begdatetime))
         drv = driver.OfflineDriver(cfg, cols, device=a.device, params=P,

@@ -7,6 +7,12 @@ achieved HBM bandwidth against their algorithmic bytes, at 1,048,576 columns.
                            one double cosine per column
   ldasin_ingest            reads 8 gathered 4-byte words + the point (36 B),
                            writes 8 rows (32 B)
+  ldasin_regrid            reads 4 corners + 4 weights (48 B) and 32 gathered
+                           words of a small 128 x 256 source grid (cache
+                           resident: not counted), writes 8 rows (32 B);
+                           bilinear, and RAINRATE + SWDOWN nearest
+  ldasin_downscale         reads dz + 4 rows (20 B), writes 4 rows (16 B); two
+                           double exponentials and five double divisions
   ldasout_grid             fills 16 grids (64 B per grid point), then reads 16
                            fluxes + the point (68 B) and scatters them (64 B)
 
@@ -69,6 +75,18 @@ def main():
     grid_be = torch.as_tensor(rng.integers(0, 2**31 - 1, (L.NLDASIN - 1, npts), dtype=np.int32),
                               device=dev)
     solar = timeman.solar_terms(172.5, 366)
+    # a 128 x 256 source around the columns of a regular model grid, in its row-major order
+    from noahmp_amd.regrid import RegridPlan, nearest_mask
+    ny = max(1, int(np.sqrt(n)))
+    nx = -(-n // ny)
+    jj, ii = np.divmod(np.arange(n), nx)
+    plan = RegridPlan.bilinear(np.linspace(24.0, 51.0, 128), np.linspace(-126.0, -65.0, 256),
+                               25.0 + 25.0 * jj / ny, -125.0 + 59.0 * ii / nx).to(dev)
+    src_be = torch.as_tensor(rng.uniform(1, 2, (L.NLDASIN - 1, plan.npts)).astype(">f4").view(
+        np.int32), device=dev)
+    dz = torch.as_tensor(rng.uniform(-500, 500, n).astype(np.float32), device=dev)
+    blk2 = torch.as_tensor(rng.uniform(250, 300, (L.NLDASIN, n)).astype(np.float32), device=dev)
+    near = nearest_mask(("RAINRATE", "SWDOWN"))
     out = []
     for prec in (4, 8):
         eng = Engine(Params.builtin(), L.CASE_NML_OPTIONS, device=0, precision=prec)
@@ -92,6 +110,14 @@ def main():
                 cases.append(("ldasin_ingest", order,
                               lambda pt=pt: eng.ldasin_ingest(grid_be, pt, blk),
                               n * (32 + 4 + 32)))
+        if prec == 4:
+            cases += [("ldasin_regrid", "bilinear",
+                       lambda: eng.ldasin_regrid(src_be, plan, blk2), n * (48 + 32)),
+                      ("ldasin_regrid", "2 nearest",
+                       lambda: eng.ldasin_regrid(src_be, plan, blk2, near), n * (48 + 32)),
+                      # (in place: repeated launches drift the block's values; timing only)
+                      ("ldasin_downscale", None,
+                       lambda: eng.ldasin_downscale(blk2, dz, 0.0065), n * (20 + 16))]
         for name, order, fn, nbytes in cases:
             ms = timed(fn, a.reps)
             gbs = nbytes / (ms * 1e-3) / 1e9

@@ -4,6 +4,12 @@ seeded synthetic generator on a regular lat-lon grid.  noahmp_offline.py then
 runs it from the files.
 
     python tools/make_offline_case.py case.nml [--ny 32 --nx 64 --kind conus]
+                                      [--forcing-grid SY SX]
+
+--forcing-grid SY SX: the LDASIN files are written on a coarser SY x SX
+rectilinear grid that covers the model grid, with a forcing-grid file
+(<input_directory>/forcing_grid.nc: the source axes, its elevation HGT and the
+model terrain HGT_M, both synthetic) for `noahmp_offline.py --forcing-grid`.
 """
 import argparse
 import os
@@ -28,6 +34,8 @@ def main(argv=None):
     ap.add_argument("--dlat", type=float, default=0.25)
     ap.add_argument("--kind", default="conus", choices=("mixed", "conus", "casenml"))
     ap.add_argument("--seed", type=int, default=0)
+    ap.add_argument("--forcing-grid", type=int, nargs=2, default=None, metavar=("SY", "SX"),
+                    help="write the LDASIN files on a coarser SY x SX grid, plus forcing_grid.nc")
     a = ap.parse_args(argv)
     cfg = config.Config(a.nmlfile)
     lat = a.lat0 + a.dlat * np.arange(a.ny)[:, None] + 0.0 * np.arange(a.nx)[None, :]
@@ -45,13 +53,47 @@ def main(argv=None):
     os.makedirs(cfg.indir, exist_ok=True)
     ncio.write_static(cfg.constfile, cols, grid)
     ncio.write_state(cfg.initfile, grid, cols.state, cols.isnow, cfg.begdatetime)
+    fcols, fgrid, where = cols, grid, ""
+    if a.forcing_grid:
+        fcols, fgrid, where = _forcing_grid(a, cfg, lat, lon, P)
     every, t, k = cfg.input_interval, cfg.begdatetime, 0
     while t < cfg.enddatetime:
-        f = cases.forcing_step(cols, timeman.julian(t), timeman.yearlen(t.year), k, seed=a.seed)
-        ncio.write_ldasin(ncio.ldasin_path(cfg.indir, t), grid, f, t, extras=False)
+        f = cases.forcing_step(fcols, timeman.julian(t), timeman.yearlen(t.year), k, seed=a.seed)
+        ncio.write_ldasin(ncio.ldasin_path(cfg.indir, t), fgrid, f, t, extras=False)
         t, k = t + every, k + 1
-    print(f"{grid.n} columns, {k} LDASIN files in {cfg.indir}; static {cfg.constfile}, "
+    print(f"{grid.n} columns, {k} LDASIN files in {cfg.indir}{where}; static {cfg.constfile}, "
           f"init {cfg.initfile}")
+
+
+def _terrain(lat, lon, fine):
+    """Synthetic terrain (m) at (lat, lon) degrees: broad ridges, plus -- on
+    the model grid -- relief the coarse grid does not resolve."""
+    h = 800.0 + 600.0 * np.sin(np.radians(lat) * 9.0) * np.cos(np.radians(lon) * 7.0)
+    if fine:
+        h = h + 150.0 * np.sin(np.radians(lat) * 160.0) * np.sin(np.radians(lon) * 140.0)
+    return np.maximum(h, 0.0)
+
+
+def _forcing_grid(a, cfg, lat, lon, P):
+    """The SY x SX source grid around the model grid (half a model cell of
+    margin), its synthetic columns for the forcing generator, and the
+    forcing-grid file."""
+    sy, sx = a.forcing_grid
+    if sy < 2 or sx < 2:
+        raise SystemExit("--forcing-grid needs at least 2 x 2 source points")
+    pad = 0.5 * a.dlat
+    slat = np.linspace(lat.min() - pad, lat.max() + pad, sy)
+    slon = np.linspace(lon.min() - pad, lon.max() + pad, sx)
+    fg = ncio.ForcingGrid(slat, slon, hgt=_terrain(slat[:, None], slon[None, :], False),
+                          hgt_m=_terrain(lat, lon, True))
+    path = os.path.join(cfg.indir, "forcing_grid.nc")
+    ncio.write_forcing_grid(path, fg)
+    sgrid = fg.as_grid()
+    scols = cases.make_columns(sgrid.n, a.kind, P, seed=a.seed + 1,
+                               julian=timeman.julian(cfg.begdatetime))
+    scols.static_f[0] = sgrid.lat_rad.astype(np.float32)
+    scols.lon = sgrid.lon_rad
+    return scols, sgrid, f" on a {sy} x {sx} source grid ({path})"
 
 
 if __name__ == "__main__":

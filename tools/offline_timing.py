@@ -20,6 +20,12 @@ LDASOUT writes).  The engine alone on the same columns with resident forcing
 is timed alongside, the ceiling the driver approaches.
 
     python tools/offline_timing.py --out profiles/r06/offline_driver.json
+
+--forcing-grid SY SX times the forcing-on-its-own-grid path instead: the same
+case with its LDASIN files on a coarse SY x SX source grid (e.g. 128 256),
+regridded on the device (nmp_ldasin_regrid), with and without the elevation
+downscaling, against the same values fed as pre-regridded model-grid files
+(nmp_ldasin_ingest) -- ms per step and bytes uploaded per input interval.
 """
 import argparse
 import json
@@ -48,11 +54,11 @@ def write_namelist(d: str) -> str:
     return p
 
 
-def time_driver(cfg, precision, ldasin, warm, steps, threads, cosz="host", ingest=False):
+def time_driver(cfg, precision, ldasin, warm, steps, threads, cosz="host", ingest=False, **kw):
     import torch
     t0 = time.perf_counter()
     drv = driver.OfflineDriver.from_files(cfg, precision=precision, ldasin_upload=ldasin,
-                                          host_threads=threads, cosz=cosz, ingest=ingest)
+                                          host_threads=threads, cosz=cosz, ingest=ingest, **kw)
     setup = time.perf_counter() - t0
     drv.run(nsteps=warm)
     torch.cuda.synchronize()
@@ -71,11 +77,14 @@ def time_driver(cfg, precision, ldasin, warm, steps, threads, cosz="host", inges
     kind = "12 fields" if drv.raw_upload is None else (
         "file bytes, device ingest + cosz" if drv.ingest is not None else
         "ldasin block + device cosz" if drv.geo is not None else "ldasin block")
+    if getattr(drv, "regrid_plan", None) is not None:
+        kind = "coarse file bytes, device regrid" + (" + downscale" if drv.downscale else "")
     res = {"precision": precision, "upload": kind, "host_threads": threads, "ncol": n,
            "steps": steps, "output_steps": outs, "uploads": puts,
            "wall_s": el, "ms_per_step": el * 1e3 / steps, "colsteps_per_s": n * steps / el,
            "phase_ms_per_step": {k: v * 1e3 / steps for k, v in drv.phase_s.items()},
            "pcie_up_bytes_per_step": bytes_per_put * puts / steps,
+           "pcie_up_bytes_per_input_interval": bytes_per_put,
            "pcie_down_bytes_per_output_step": L.NDIAG_OUT * precision * n,
            "setup_s": setup,
            "status_nonzero_cols": int((drv.cs.status != 0).sum().item())}
@@ -108,8 +117,50 @@ def time_engine(drv_like, precision, steps):
             "colsteps_per_s": cs.ncol * steps / el}
 
 
+def coarse_forcing_runs(a, nml):
+    """The case on a coarse source grid, device-regridded (with and without
+    downscaling), against pre-regridded model-grid files of the same values."""
+    import make_offline_case
+    from noahmp_amd import ncio
+    from noahmp_amd.params import Params
+    make_offline_case.main([nml, "--ny", str(a.ny), "--nx", str(a.nx), "--kind", "mixed",
+                            "--forcing-grid", *[str(v) for v in a.forcing_grid]])
+    cfg = config.Config(nml)
+    coarse = cfg.indir
+    fgpath = os.path.join(coarse, "forcing_grid.nc")
+    grid, _, _ = ncio.read_static(cfg.constfile, Params.builtin().as_dict(), cfg.begdatetime)
+    fr = ncio.LdasinForcing(coarse, grid, cfg.begdatetime, cfg.input_interval,
+                            src=ncio.read_forcing_grid(fgpath))
+    pre = os.path.join(a.dir, "ldasin_model")
+    os.makedirs(pre, exist_ok=True)
+    inv = {v: k for k, v in ncio.LDASIN_MAP.items()}
+    t = cfg.begdatetime
+    while t < cfg.enddatetime:
+        cols8 = fr.plan.apply_host(fr.grid_raw(t))
+        f12 = np.zeros((L.NFORCING, grid.n), np.float32)
+        for i, var in enumerate(L.LDASIN[:-1]):
+            f12[L.FORCING.index(inv[var])] = cols8[i]
+        ncio.write_ldasin(ncio.ldasin_path(pre, t), grid, f12, t, extras=False)
+        t = t + cfg.input_interval
+    print(f"pre-regridded model-grid files written to {pre}", flush=True)
+    runs, states = [], []
+    for indir, kw in ((pre, {}), (coarse, dict(forcing_grid=fgpath)),
+                      (coarse, dict(forcing_grid=fgpath, downscale=True))):
+        cfg.indir = indir
+        r, st, drv = time_driver(cfg, 4, True, a.warm, a.steps, a.threads, "device", True, **kw)
+        states.append(st)
+        r["state_equals_first_run"] = bool(np.array_equal(states[0].view(np.uint8),
+                                                          st.view(np.uint8)))
+        print(json.dumps(r), flush=True)
+        runs.append(r)
+        del drv
+    return runs
+
+
 def main():
     ap = argparse.ArgumentParser()
+    ap.add_argument("--forcing-grid", type=int, nargs=2, default=None, metavar=("SY", "SX"),
+                    help="time the coarse-forcing path against pre-regridded files instead")
     ap.add_argument("--ny", type=int, default=1024)
     ap.add_argument("--nx", type=int, default=1024)
     ap.add_argument("--dir", default=os.path.join(os.environ.get("TMPDIR", "/tmp"), "nmp_case"))
@@ -121,6 +172,15 @@ def main():
     a = ap.parse_args()
     os.makedirs(a.dir, exist_ok=True)
     nml = write_namelist(a.dir)
+    if a.forcing_grid:
+        runs = coarse_forcing_runs(a, nml)
+        if a.out:
+            os.makedirs(os.path.dirname(os.path.abspath(a.out)), exist_ok=True)
+            with open(a.out, "w") as f:
+                json.dump({"case": f"{a.ny} x {a.nx} land points, LDASIN on a "
+                                   f"{a.forcing_grid[0]} x {a.forcing_grid[1]} source grid",
+                           "driver": runs}, f, indent=1)
+        return 0
     import make_offline_case
     t0 = time.perf_counter()
     make_offline_case.main([nml, "--ny", str(a.ny), "--nx", str(a.nx), "--kind", "mixed"])
