@@ -31,14 +31,20 @@ struct Mth<double, REF> {
   NMP_MATH_FN double exp2(double x) { return ::exp2(x); }
   NMP_MATH_FN double log(double x) { return ::log(x); }
   NMP_MATH_FN double log10(double x) { return ::log10(x); }
-  // x**y as exp(y log x): within |y log x| ulp of pow, which is far inside the
-  // fp64 path's tolerances, at about half the cost of ocml's double pow (that
-  // one carries log x in double-double).  Every base in the kernel is >= 0;
-  // 0**y (y > 0) -> exp(-inf) = 0 as pow gives.
+  // x**y as exp(y log x): with log within E_log ulp and exp within E_exp ulp
+  // (ocml's measured maxima: profiles/math64/ulp.json), t = y log x carries a
+  // relative error <= (E_log + 0.5) 2^-52, which exp turns into at most
+  // 2 (E_log + 0.5) |y log x| + E_exp ulp of the correctly rounded pow
+  // (tests/test_gpu_math64.py asserts it): NOT "within |y log x| ulp", the
+  // error grows with |y log x| and does not vanish with it.  That is still far
+  // inside the fp64 path's tolerances, at about half the cost of ocml's double pow
+  // (that one carries log x in double-double).  Every base in the kernel is
+  // >= 0; 0**y (y > 0) -> exp(-inf) = 0 as pow gives.
   NMP_MATH_FN double pow(double x, double y) { return exp(y * ::log(x)); }
   // x**0.25 and x**(-0.25): the fp64 path is held to a tolerance, not to bits
-  // (DESIGN.md "fp64"), so the fourth root is two square roots (<= 1 ulp from
-  // pow, and ~10x cheaper than ocml's double pow)
+  // (DESIGN.md "fp64"), so the fourth root is two correctly rounded square
+  // roots (<= 1.5 ulp from the correctly rounded pow; the reciprocal's rounding
+  // makes pow_mq <= 2.5 ulp; ~10x cheaper than ocml's double pow)
   NMP_MATH_FN double pow_q(double x) { return ::sqrt(::sqrt(x)); }
   NMP_MATH_FN double pow_mq(double x) { return 1.0 / ::sqrt(::sqrt(x)); }
   NMP_MATH_FN double tanh(double x) { return ::tanh(x); }

@@ -11,6 +11,10 @@
 //   dv     the fp64 Newton-loop division (csrc/sflx_math.h), against IEEE `/`
 //   sqrt_normal32 / DivFast32: the short fp32 sqrt and division of the
 //          range-proven sites, exhaustively / at the edges of their exact region
+//   math   the exact float libm (csrc/glibc_math.h) through Mth<float, true> and
+//          pow_pair, against the host compilation of the same header (sweep and
+//          list entries, tests/test_gpu_math.py); Mth<double, true>'s functions
+//          as a list entry (tests/test_gpu_math64.py, against mpmath goldens)
 // tests/test_gpu_routines.py compares them bit for bit with the oracle's C
 // restatement of each routine, and frh2o also with the reference's own
 // (public) frh2o.  Built by __graft_entry__.build() into tests/lib/.
@@ -160,6 +164,134 @@ __global__ void k_div32_edge(int ea, int eb, unsigned sa, unsigned oa, unsigned 
   if (nout) atomicAdd(&cnt[2], nout);
 }
 
+// ---- the math primitives on their own ---------------------------------------
+// Function ids shared by the fp32 and fp64 entries below.
+enum MathFn {
+  M_EXP = 0, M_EXP2, M_LOG, M_LOG10, M_TANH, M_ATAN, M_TAN, M_ACOS, M_COS,
+  M_EXPM1_OR_SQRT,  // fp32: gm::expm1f (tanhf's helper); fp64: Mth::sqrt
+  M_POW, M_POW_Q, M_POW_MQ, M_POW_PAIR, M_NFN
+};
+
+// fp32: the exact float libm (csrc/glibc_math.h) as the step kernel calls it,
+// tables staged in LDS by the workgroup, through Mth<float, true> and pow_pair
+using M32 = nmp::Mth<float, true>;
+template <int FN>
+__device__ __forceinline__ void m32_dev(float x, float y1, float y2, float& r1, float& r2) {
+  r2 = 0.0f;
+  if constexpr (FN == M_EXP) r1 = M32::exp(x);
+  else if constexpr (FN == M_EXP2) r1 = M32::exp2(x);
+  else if constexpr (FN == M_LOG) r1 = M32::log(x);
+  else if constexpr (FN == M_LOG10) r1 = M32::log10(x);
+  else if constexpr (FN == M_TANH) r1 = M32::tanh(x);
+  else if constexpr (FN == M_ATAN) r1 = M32::atan(x);
+  else if constexpr (FN == M_TAN) r1 = M32::tan(x);
+  else if constexpr (FN == M_ACOS) r1 = M32::acos(x);
+  else if constexpr (FN == M_COS) r1 = M32::cos(x);
+  else if constexpr (FN == M_EXPM1_OR_SQRT) r1 = gm::expm1f(x);
+  else if constexpr (FN == M_POW) r1 = M32::pow(x, y1);
+  else if constexpr (FN == M_POW_Q) r1 = M32::pow_q(x);
+  else if constexpr (FN == M_POW_MQ) r1 = M32::pow_mq(x);
+  else nmp::pow_pair<float, true>(x, y1, y2, r1, r2);
+}
+
+// The same header as compiled for the host (the __host__ half of GM_HD), with
+// a static table: the reference of the fp32 entries.  pow_q / pow_mq are by
+// definition pow(x, +-0.25f).
+const gm::GmTables kHostTab = {GM_EXP2F_TAB, GM_LOGF_TAB, GM_POWF_TAB};
+void m32_host(int fn, float x, float y1, float y2, float& r1, float& r2) {
+  r2 = 0.0f;
+  switch (fn) {
+    case M_EXP: r1 = gm::expf(x, kHostTab); break;
+    case M_EXP2: r1 = gm::exp2f(x, kHostTab); break;
+    case M_LOG: r1 = gm::logf(x, kHostTab); break;
+    case M_LOG10: r1 = gm::log10f(x, kHostTab); break;
+    case M_TANH: r1 = gm::tanhf(x); break;
+    case M_ATAN: r1 = gm::atanf(x); break;
+    case M_TAN: r1 = gm::tanf(x); break;
+    case M_ACOS: r1 = gm::acosf(x); break;
+    case M_COS: r1 = gm::cosf(x); break;
+    case M_EXPM1_OR_SQRT: r1 = gm::expm1f(x); break;
+    case M_POW: r1 = gm::powf(x, y1, kHostTab); break;
+    case M_POW_Q: r1 = gm::powf(x, 0.25f, kHostTab); break;
+    case M_POW_MQ: r1 = gm::powf(x, -0.25f, kHostTab); break;
+    default: gm::powf_pair(x, y1, y2, kHostTab, r1, r2); break;
+  }
+}
+
+// Input i is the bit pattern xs[i] (list) or, with xs null, first +
+// (base + i) * stride modulo 2^32 (sweep); the exponents are y1s[i] / y2s[i]
+// where those arrays are given, the scalars otherwise.  Result bits out.
+template <int FN>
+__global__ void k_m32(unsigned n, const unsigned* xs, const unsigned* y1s, const unsigned* y2s,
+                      unsigned first, unsigned stride, unsigned long long base, float y1, float y2,
+                      unsigned* o1, unsigned* o2) {
+  nmp::stage_math_tables();
+  __syncthreads();
+  const unsigned i = blockIdx.x * blockDim.x + threadIdx.x;
+  if (i >= n) return;
+  const unsigned u = xs ? xs[i] : first + (unsigned)((base + i) * stride);
+  if (y1s) y1 = __uint_as_float(y1s[i]);
+  if (y2s) y2 = __uint_as_float(y2s[i]);
+  float r1, r2;
+  m32_dev<FN>(__uint_as_float(u), y1, y2, r1, r2);
+  o1[i] = __float_as_uint(r1);
+  if (FN == M_POW_PAIR) o2[i] = __float_as_uint(r2);
+}
+
+using K32 = void (*)(unsigned, const unsigned*, const unsigned*, const unsigned*, unsigned,
+                     unsigned, unsigned long long, float, float, unsigned*, unsigned*);
+K32 m32_kernel(int fn) {
+  static const K32 k[M_NFN] = {k_m32<0>, k_m32<1>, k_m32<2>,  k_m32<3>,  k_m32<4>,
+                               k_m32<5>, k_m32<6>, k_m32<7>,  k_m32<8>,  k_m32<9>,
+                               k_m32<10>, k_m32<11>, k_m32<12>, k_m32<13>};
+  return k[fn];
+}
+
+// fp64: Mth<double, true> and pow_pair<double, true>, the fp64 engine's math
+using M64 = nmp::Mth<double, true>;
+template <int FN>
+__global__ void k_m64(unsigned n, const double* xs, const double* y1s, const double* y2s,
+                      double* o1, double* o2) {
+  const unsigned i = blockIdx.x * blockDim.x + threadIdx.x;
+  if (i >= n) return;
+  const double x = xs[i], y1 = y1s ? y1s[i] : 0.0, y2 = y2s ? y2s[i] : 0.0;
+  double r1, r2 = 0.0;
+  if constexpr (FN == M_EXP) r1 = M64::exp(x);
+  else if constexpr (FN == M_EXP2) r1 = M64::exp2(x);
+  else if constexpr (FN == M_LOG) r1 = M64::log(x);
+  else if constexpr (FN == M_LOG10) r1 = M64::log10(x);
+  else if constexpr (FN == M_TANH) r1 = M64::tanh(x);
+  else if constexpr (FN == M_ATAN) r1 = M64::atan(x);
+  else if constexpr (FN == M_TAN) r1 = M64::tan(x);
+  else if constexpr (FN == M_ACOS) r1 = M64::acos(x);
+  else if constexpr (FN == M_COS) r1 = M64::cos(x);
+  else if constexpr (FN == M_EXPM1_OR_SQRT) r1 = M64::sqrt(x);
+  else if constexpr (FN == M_POW) r1 = M64::pow(x, y1);
+  else if constexpr (FN == M_POW_Q) r1 = M64::pow_q(x);
+  else if constexpr (FN == M_POW_MQ) r1 = M64::pow_mq(x);
+  else nmp::pow_pair<double, true>(x, y1, y2, r1, r2);
+  o1[i] = r1;
+  if (FN == M_POW_PAIR) o2[i] = r2;
+}
+
+using K64 = void (*)(unsigned, const double*, const double*, const double*, double*, double*);
+K64 m64_kernel(int fn) {
+  static const K64 k[M_NFN] = {k_m64<0>, k_m64<1>, k_m64<2>,  k_m64<3>,  k_m64<4>,
+                               k_m64<5>, k_m64<6>, k_m64<7>,  k_m64<8>,  k_m64<9>,
+                               k_m64<10>, k_m64<11>, k_m64<12>, k_m64<13>};
+  return k[fn];
+}
+
+bool math_args_ok(int fn, int threads) {
+  return fn >= 0 && fn < M_NFN && threads >= 1 && threads <= 1024;
+}
+unsigned f2u(float f) { return __builtin_bit_cast(unsigned, f); }
+float u2f(unsigned u) { return __builtin_bit_cast(float, u); }
+// the checkers' equality: equal bits, or both NaN
+bool same32(unsigned a, unsigned b) {
+  return a == b || ((a & 0x7fffffffu) > 0x7f800000u && (b & 0x7fffffffu) > 0x7f800000u);
+}
+
 // host helpers: device copies in, one launch, results out (synchronous)
 struct Dev {
   std::vector<void*> ptrs;
@@ -304,6 +436,118 @@ int rt_div32_edge(int ea, int eb, unsigned sa, unsigned oa, unsigned sb, unsigne
   if (hipDeviceSynchronize() != hipSuccess) return -4;
   if (hipMemcpy(cnt3, dc, 3 * sizeof(*dc), hipMemcpyDeviceToHost) != hipSuccess) return -4;
   return hipMemcpy(first, df, sizeof(*df), hipMemcpyDeviceToHost) == hipSuccess ? 0 : -4;
+}
+
+// fp32 math, sweep form: function `fn` (MathFn) over the `count` bit patterns
+// first, first + stride, ... (modulo 2^32), exponents y1 (pow) or y1, y2
+// (pow_pair), launched with `threads` per block; the device's result bits
+// against the host compilation of the same header.  dom120 != 0 leaves inputs
+// that are not |x| < 120 out of the comparison (gm::cosf / gm::tanf restate
+// glibc only there).  res7 = {inputs compared, mismatching results, first
+// mismatching input pattern, its device bits, its host bits, host results that
+// are subnormal and nonzero, which result of a pair (0 / 1) mismatched}.
+int rt_math32_sweep(int fn, unsigned first, unsigned long long count, unsigned stride, float y1,
+                    float y2, int dom120, int threads, unsigned long long* res7) {
+  if (!math_args_ok(fn, threads) || count == 0 || count > (1ull << 32)) return -1;
+  constexpr unsigned kChunk = 1u << 22;
+  const bool pair = fn == M_POW_PAIR;
+  Dev D;
+  const size_t cap = count < kChunk ? (size_t)count : kChunk;
+  unsigned *d1 = D.in<unsigned>(nullptr, cap), *d2 = D.in<unsigned>(nullptr, cap);
+  if (!d1 || !d2) return -4;
+  std::vector<unsigned> g1(cap), g2(cap), h1(cap), h2(cap);
+  for (int k = 0; k < 7; ++k) res7[k] = 0;
+  const K32 kern = m32_kernel(fn);
+  for (unsigned long long base = 0; base < count; base += kChunk) {
+    const unsigned n = (unsigned)(count - base < kChunk ? count - base : kChunk);
+    hipLaunchKernelGGL(kern, dim3((n + threads - 1) / threads), dim3(threads), 0, 0, n,
+                       (const unsigned*)nullptr, (const unsigned*)nullptr, (const unsigned*)nullptr,
+                       first, stride, base, y1, y2, d1, d2);
+    if (hipGetLastError() != hipSuccess) return -4;
+    // the host's results while the device works on its own
+    for (unsigned i = 0; i < n; ++i) {
+      float r1, r2;
+      m32_host(fn, u2f(first + (unsigned)((base + i) * stride)), y1, y2, r1, r2);
+      h1[i] = f2u(r1);
+      h2[i] = f2u(r2);
+    }
+    if (hipDeviceSynchronize() != hipSuccess) return -4;
+    if (hipMemcpy(g1.data(), d1, n * sizeof(unsigned), hipMemcpyDeviceToHost) != hipSuccess)
+      return -4;
+    if (pair && hipMemcpy(g2.data(), d2, n * sizeof(unsigned), hipMemcpyDeviceToHost) != hipSuccess)
+      return -4;
+    for (unsigned i = 0; i < n; ++i) {
+      const unsigned u = first + (unsigned)((base + i) * stride);
+      if (dom120 && !(fabsf(u2f(u)) < 120.0f)) continue;
+      ++res7[0];
+      for (int j = 0; j < (pair ? 2 : 1); ++j) {
+        const unsigned g = j ? g2[i] : g1[i], h = j ? h2[i] : h1[i];
+        if ((h & 0x7f800000u) == 0 && (h & 0x007fffffu) != 0) ++res7[5];
+        if (same32(g, h)) continue;
+        if (res7[1]++ == 0) {
+          res7[2] = u;
+          res7[3] = g;
+          res7[4] = h;
+          res7[6] = j;
+        }
+      }
+    }
+  }
+  return 0;
+}
+
+// fp32 math, list form: inputs x[i] (and y1[i], y2[i] where the function takes
+// them; null otherwise) as bit patterns in, device bits and host bits out
+// (dev2 / host2: pow_pair's second result, null otherwise)
+int rt_math32_list(int fn, int n, const unsigned* x, const unsigned* y1, const unsigned* y2,
+                   int threads, unsigned* dev1, unsigned* host1, unsigned* dev2, unsigned* host2) {
+  if (!math_args_ok(fn, threads) || n <= 0) return -1;
+  const bool pair = fn == M_POW_PAIR;
+  if ((fn >= M_POW && fn != M_POW_Q && fn != M_POW_MQ && !y1) || (pair && (!y2 || !dev2 || !host2)))
+    return -1;
+  Dev D;
+  const unsigned* dx = D.in(x, n);
+  const unsigned* dy1 = y1 ? D.in(y1, n) : nullptr;
+  const unsigned* dy2 = y2 ? D.in(y2, n) : nullptr;
+  unsigned *d1 = D.in<unsigned>(nullptr, n), *d2 = D.in<unsigned>(nullptr, n);
+  if (!dx || (y1 && !dy1) || (y2 && !dy2) || !d1 || !d2) return -4;
+  hipLaunchKernelGGL(m32_kernel(fn), dim3(((unsigned)n + threads - 1) / threads), dim3(threads), 0,
+                     0, (unsigned)n, dx, dy1, dy2, 0u, 0u, 0ull, 0.0f, 0.0f, d1, d2);
+  if (hipGetLastError() != hipSuccess) return -4;
+  for (int i = 0; i < n; ++i) {
+    float r1, r2;
+    m32_host(fn, u2f(x[i]), y1 ? u2f(y1[i]) : 0.0f, y2 ? u2f(y2[i]) : 0.0f, r1, r2);
+    host1[i] = f2u(r1);
+    if (pair) host2[i] = f2u(r2);
+  }
+  if (hipDeviceSynchronize() != hipSuccess) return -4;
+  if (hipMemcpy(dev1, d1, n * sizeof(unsigned), hipMemcpyDeviceToHost) != hipSuccess) return -4;
+  if (pair && hipMemcpy(dev2, d2, n * sizeof(unsigned), hipMemcpyDeviceToHost) != hipSuccess)
+    return -4;
+  return 0;
+}
+
+// fp64 math, list form: Mth<double, true> (fn 9 = sqrt) and pow_pair<double,
+// true> on x[i] (, y1[i], y2[i]); the results out (out2: pow_pair's second)
+int rt_math64_list(int fn, int n, const double* x, const double* y1, const double* y2, int threads,
+                   double* out1, double* out2) {
+  if (!math_args_ok(fn, threads) || n <= 0) return -1;
+  const bool pair = fn == M_POW_PAIR;
+  if (((fn == M_POW || pair) && !y1) || (pair && (!y2 || !out2))) return -1;
+  Dev D;
+  const double* dx = D.in(x, n);
+  const double* dy1 = y1 ? D.in(y1, n) : nullptr;
+  const double* dy2 = y2 ? D.in(y2, n) : nullptr;
+  double *d1 = D.in<double>(nullptr, n), *d2 = D.in<double>(nullptr, n);
+  if (!dx || (y1 && !dy1) || (y2 && !dy2) || !d1 || !d2) return -4;
+  hipLaunchKernelGGL(m64_kernel(fn), dim3(((unsigned)n + threads - 1) / threads), dim3(threads), 0,
+                     0, (unsigned)n, dx, dy1, dy2, d1, d2);
+  if (hipGetLastError() != hipSuccess) return -4;
+  if (hipDeviceSynchronize() != hipSuccess) return -4;
+  if (hipMemcpy(out1, d1, n * sizeof(double), hipMemcpyDeviceToHost) != hipSuccess) return -4;
+  if (pair && hipMemcpy(out2, d2, n * sizeof(double), hipMemcpyDeviceToHost) != hipSuccess)
+    return -4;
+  return 0;
 }
 
 }  // extern "C"
