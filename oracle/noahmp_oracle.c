@@ -39,6 +39,22 @@ void oracle_set_stats(int32_t* buf) { g_stats = buf; }
 #define ITER_STAT(k) ((void)0)
 #endif
 
+/* Rare-branch markers (build with -DORACLE_BRANCH_STATS only; port.step_branches,
+ * tests/test_branch_golden.py): BR(id) sits in the body of a physics branch
+ * that plausible climates never take and sets bit `id` of the column's mask
+ * (port.BRANCH_SITES names the bits).  The arithmetic is unchanged. */
+#ifdef ORACLE_BRANCH_STATS
+static uint32_t* g_br;
+static int32_t g_br_col;
+void oracle_set_branches(uint32_t* buf) { g_br = buf; }
+#define BR(id)                                        \
+  do {                                                \
+    if (g_br) g_br[g_br_col] |= (uint32_t)1 << (id);  \
+  } while (0)
+#else
+#define BR(id) ((void)0)
+#endif
+
 /* Division operand ranges of the canopy Newton loop (vege_flux with sfcdif1
  * and ragrb; build with -DORACLE_DIV_STATS only, tools/div_ranges.py): per
  * site the smallest / largest |a|, |b|, |a/b| over nonzero finite values and
@@ -346,6 +362,7 @@ static void snowage(const nmp_params* P, real DT, real TG, real SNEQVO, real sne
   if (sneqv <= K(0.0)) {
     *TAUSS = K(0.0);
   } else if (sneqv > K(800.0)) {
+    BR(0);
     *TAUSS = K(0.0);
   } else {
     real DELA0 = K(1.0E-6) * DT;
@@ -407,6 +424,7 @@ static void groundalb(const nmp_params* P, int IST, int ISC, real FSNO, const re
       ALBSOI = ALBSOD;
     }
     if (IST == 1 && ISC == 9) {
+      BR(1);
       ALBSOD = ALBSOD + K(0.10);
       ALBSOI = ALBSOI + K(0.10);
     }
@@ -733,8 +751,10 @@ static void sfcdif2(int iter, real Z0, real THZ0, real THLM, real SFCSPD, real C
   if (iter == 1) {
     if (BTGH * *AKHS * DTHV != K(0.0))
       *WSTAR2 = WWST2 * POW(FABS(BTGH * *AKHS * DTHV), K(2.0) / K(3.0));
-    else
+    else {
+      BR(2);
       *WSTAR2 = K(0.0);
+    }
     *USTAR = rmax(SQRT(*AKMS * SQRT(DU2 + *WSTAR2)), EPSUST);
     *RLMO = ELFC * *AKHS * DTHV / p3(*USTAR);
   }
@@ -782,8 +802,10 @@ static void sfcdif2(int iter, real Z0, real THZ0, real THLM, real SFCSPD, real C
   *AKHS = rmax(USTARK / SIMH, CXCH);
   if (BTGH * *AKHS * DTHV != K(0.0))
     *WSTAR2 = WWST2 * POW(FABS(BTGH * *AKHS * DTHV), K(2.0) / K(3.0));
-  else
+  else {
+    BR(23);
     *WSTAR2 = K(0.0);
+  }
   real RLMN = ELFC * *AKHS * DTHV / p3(*USTAR);
   real RLMA = *RLMO * WOLD + RLMN * WNEW;
   *RLMO = RLMA;
@@ -843,6 +865,7 @@ static void stomata(const nmp_params* P, int lutyp, real igs, real sfcprs, real 
   real rlb = rb / cf;
   real cihigh = K(1.5) * co2, cilow = K(0.0);
   const int c3c4 = P->c3c4[lutyp - 1];
+  int b_nonneg = 0; /* branch marker only: the root taken by the last iteration */
   for (int iter = 1; iter <= 20; ++iter) { ITER_STAT(1);
     real ci = K(0.5) * (cihigh + cilow);
     /* ci2ci: func.f90:3847-3886.  The reference keeps wc/wj/we SAVEd (nan4
@@ -853,6 +876,7 @@ static void stomata(const nmp_params* P, int lutyp, real igs, real sfcprs, real 
       wc = rmax(ci - cp, K(0.0)) * vcmx / (ci + awc);
       we = K(0.5) * vcmx;
     } else if (c3c4 == 2) {
+      BR(3);
       wj = j;
       wc = vcmx;
       we = K(4000.0) * vcmx * ci / sfcprs;
@@ -863,10 +887,13 @@ static void stomata(const nmp_params* P, int lutyp, real igs, real sfcprs, real 
     real b = (VEGP(mp) * *psn * sfcprs / cs + VEGP(bp)) * rlb - K(1.0);
     real c = -rlb;
     real q;
-    if (b >= K(0.0))
+    if (b >= K(0.0)) {
       q = K(-0.5) * (b + SQRT(b * b - K(4.0) * a * c));
-    else
+      b_nonneg = 1;
+    } else {
       q = K(-0.5) * (b - SQRT(b * b - K(4.0) * a * c));
+      b_nonneg = 0;
+    }
     real r1 = q / a;
     real r2 = c / q;
     *rs = rmax(r1, r2);
@@ -877,6 +904,7 @@ static void stomata(const nmp_params* P, int lutyp, real igs, real sfcprs, real 
     else
       cihigh = ci;
   }
+  if (b_nonneg) BR(4);
   *rs = *rs * cf;
 }
 
@@ -1080,6 +1108,7 @@ static void vege_flux(ctx_t* X, int ISNOW, int lutyp, real DT, real SAV, real SA
     o->CAH2 = FV * KARMAN / (LOG((K(2.0) + Z0H) / Z0H) - FH2);
     real CQ2V = o->CAH2;
     if (o->CAH2 < K(1.E-5)) {
+      BR(5);
       o->T2MV = *TAH;
       o->Q2V = *QSFC;
     } else {
@@ -1176,6 +1205,7 @@ static void bare_flux(ctx_t* X, int lutyp, int ISNOW, real SAG, real LWDN, real 
     o->EHB2 = FV * KARMAN / (LOG((K(2.0) + Z0H) / Z0H) - FH2);
     real CQ2B = o->EHB2;
     if (o->EHB2 < K(1.0E-5)) {
+      BR(6);
       o->T2MB = *TGB;
       o->Q2B = *QSFC;
     } else {
@@ -1300,6 +1330,7 @@ static real frh2o(ctx_t* X, int sltyp, real TKELV, real SMC, real soilwat) {
     }
     FREE = SMC - SWL;
     if (KCOUNT == 0) {
+      BR(7);
       X->status |= NMP_ST_FLERCH;
       real FK = POW((HFUS / (GRAV * (-SOILP(psisat)))) * ((TKELV - TFRZ) / TKELV), K(-1.0) / BX) *
                 SOILP(smcmax);
@@ -1367,10 +1398,12 @@ static void phasechange(ctx_t* X, int sltyp, int ISNOW, real DT, const real* FAC
       STC[J] = TFRZ;
     }
     if (IMELT[J] == 1 && HM[J] < K(0.0)) {
+      BR(8);
       HM[J] = K(0.0);
       IMELT[J] = 0;
     }
     if (IMELT[J] == 2 && HM[J] > K(0.0)) {
+      BR(8);
       HM[J] = K(0.0);
       IMELT[J] = 0;
     }
@@ -1404,6 +1437,7 @@ static void phasechange(ctx_t* X, int sltyp, int ISNOW, real DT, const real* FAC
           MICE[J] = rmin(WMASS0[J], WICE0[J] - XM[J]);
         } else {
           if (WMASS0[J] < SUPERCOOL[J]) {
+            BR(9);
             MICE[J] = K(0.0);
           } else {
             MICE[J] = rmin(WMASS0[J] - SUPERCOOL[J], WICE0[J] - XM[J]);
@@ -1603,8 +1637,10 @@ static void combine(int* ISNOW, real* soilwat, real* STC, real* SNICE, real* SNL
             *sneqv = SNICE[J];
             *snowh = DZSNSO[J];
           } else {
+            BR(10);
             *PONDING1 = SNLIQ[J] + SNICE[J];
             if (*PONDING1 < K(0.0)) {
+              BR(22);
               soilice[1] = rmax(K(0.0), soilice[1] + *PONDING1 / (DZSNSO[1] * K(1000.0)));
               *PONDING1 = K(0.0);
             }
@@ -1628,6 +1664,7 @@ static void combine(int* ISNOW, real* soilwat, real* STC, real* SNICE, real* SNL
     }
   }
   if (soilice[1] < K(0.0)) {
+    BR(11);
     soilwat[1] = soilwat[1] + soilice[1];
     soilice[1] = K(0.0);
   }
@@ -1658,8 +1695,12 @@ static void combine(int* ISNOW, real* soilwat, real* STC, real* SNICE, real* SNL
         } else if (I == 0) {
           NEIBOR = I - 1;
         } else {
+          BR(12);
           NEIBOR = I + 1;
-          if ((DZSNSO[I - 1] + DZSNSO[I]) < (DZSNSO[I + 1] + DZSNSO[I])) NEIBOR = I - 1;
+          if ((DZSNSO[I - 1] + DZSNSO[I]) < (DZSNSO[I + 1] + DZSNSO[I])) {
+            BR(13);
+            NEIBOR = I - 1;
+          }
         }
         int J, L;
         if (NEIBOR > I) {
@@ -1805,6 +1846,7 @@ static void snowh2o(const nmp_params* P, real DT, real QSNFRO, real QSNSUB, real
   if (*sneqv == K(0.0)) {
     soilice[1] = soilice[1] + (QSNFRO - QSNSUB) * DT / (DZSNSO[1] * K(1000.0));
     if (soilice[1] < K(0.0)) {
+      BR(14);
       soilwat[1] = soilwat[1] + soilice[1];
       soilice[1] = K(0.0);
     }
@@ -1820,6 +1862,7 @@ static void snowh2o(const nmp_params* P, real DT, real QSNFRO, real QSNSUB, real
       *snowh = K(0.0);
     }
     if (soilice[1] < K(0.0)) {
+      BR(15);
       soilwat[1] = soilwat[1] + soilice[1];
       soilice[1] = K(0.0);
     }
@@ -1831,8 +1874,10 @@ static void snowh2o(const nmp_params* P, real DT, real QSNFRO, real QSNSUB, real
   if (*ISNOW < 0) {
     real WGDIF = SNICE[*ISNOW + 1] - QSNSUB * DT + QSNFRO * DT;
     SNICE[*ISNOW + 1] = WGDIF;
-    if (WGDIF < K(1.0E-6) && *ISNOW < 0)
+    if (WGDIF < K(1.0E-6) && *ISNOW < 0) {
+      BR(16);
       combine(ISNOW, soilwat, STC, SNICE, SNLIQ, DZSNSO, soilice, snowh, sneqv, PONDING1, PONDING2);
+    }
     if (*ISNOW < 0) {
       SNLIQ[*ISNOW + 1] = SNLIQ[*ISNOW + 1] + QRAIN * DT;
       SNLIQ[*ISNOW + 1] = rmax(K(0.0), SNLIQ[*ISNOW + 1]);
@@ -1851,6 +1896,7 @@ static void snowh2o(const nmp_params* P, real DT, real QSNFRO, real QSNSUB, real
       SNLIQ[J] = SNLIQ[J] + QIN;
       if (J <= -1) {
         if (epore[J] < K(0.05) || epore[J + 1] < K(0.05)) {
+          BR(17);
           QOUT = K(0.0);
         } else {
           QOUT = rmax(K(0.0), (VOL_LIQ[J] - (real)P->ssi * epore[J]) * DZSNSO[J]);
@@ -1892,6 +1938,7 @@ static void snowwater(ctx_t* X, real dt, const real* zsoil, const int* IMELT, re
     ZSNSO[iz] = K(0.0);
   }
   if (*sneqv > K(2000.0)) {
+    BR(18);
     real BDSNOW = SNICE[0] / DZSNSO[0];
     *SNOFLOW = (*sneqv - K(2000.0));
     SNICE[0] = SNICE[0] - *SNOFLOW;
@@ -2253,6 +2300,7 @@ static void groundwater(const nmp_params* P, int sltyp, real DT, const real* ZSO
     if (IWT == NSOIL - 1) {
       *ZWT = -ZSOIL[NSOIL] - (*WT - ROUS * K(1000.0) * K(25.0)) / (epore[NSOIL]) / K(1000.0);
     } else {
+      BR(19);
       real WS = K(0.0);
       for (int iz = IWT + 2; iz <= NSOIL; ++iz) WS = WS + epore[iz] * DZMM[iz];
       *ZWT = -ZSOIL[IWT + 1] - (*WT - ROUS * K(1000.0) * K(25.0) - WS) / (epore[IWT + 1]) / K(1000.0);
@@ -2409,6 +2457,7 @@ static void carbon(const nmp_params* P, int lutyp, real DT, const real* ZSOIL, c
   *STMASS = *STMASS + (NPPS - STTOVR - DIEST) * DT;
   *RTMASS = *RTMASS + (NPPR - RTTOVR) * DT;
   if (*RTMASS < K(0.0)) {
+    BR(20);
     RTTOVR = NPPR;
     *RTMASS = K(0.0);
   }
@@ -2511,6 +2560,7 @@ static void sflx_column(ctx_t* X, real DT, int YEARLEN, real JULIAN, const real 
     fveg = SHDMAX;
     if (fveg <= K(0.01)) fveg = K(0.01);
   } else {
+    BR(21);
     X->status |= NMP_ST_OPTVEG;
   }
   if (lutyp == P->isurban || lutyp == P->isbarren) fveg = K(0.0);
@@ -2792,6 +2842,9 @@ int oracle_sflx_batch(int32_t n, real dt, int32_t yearlen, real julian, const re
   for (int32_t c = 0; c < n; ++c) {
 #ifdef ORACLE_ITER_STATS
     g_stat_col = c;
+#endif
+#ifdef ORACLE_BRANCH_STATS
+    g_br_col = c;
 #endif
     ctx_t X = {P, O, 0};
     sflx_column(&X, dt, yearlen, julian, zsoil, st + (size_t)c * NMP_NSTATE, isnow + c,

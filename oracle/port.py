@@ -19,10 +19,24 @@ LIBS = {4: os.path.join(HERE, "build", "liboracle_f32.so"),
         "cr": os.path.join(HERE, "build", "liboracle_f32cr.so"),
         "4s": os.path.join(HERE, "build", "liboracle_f32_stats.so"),
         "8s": os.path.join(HERE, "build", "liboracle_f64_stats.so"),
-        "4d": os.path.join(HERE, "build", "liboracle_f32_divstats.so")}
+        "4d": os.path.join(HERE, "build", "liboracle_f32_divstats.so"),
+        "4b": os.path.join(HERE, "build", "liboracle_f32_brstats.so"),
+        "8b": os.path.join(HERE, "build", "liboracle_f64_brstats.so")}
 # trip counts recorded by the stats builds, per column (noahmp_oracle.c ITER_STAT)
 STAT_LOOPS = ("vege_flux Newton", "stomata bisection", "frh2o", "soilwater sub-steps",
               "bare_flux Newton")
+# bit k of the branch-marker builds' per-column mask (noahmp_oracle.c BR(k)): the
+# physics branches that columns from cases.make_columns / forcing_random never
+# take, pinned by tests/golden/branch_*.npz
+BRANCH_SITES = (
+    "snowage_sneqv_over_800", "groundalb_soilcolor_9", "sfcdif2_wstar2_zero_first", "stomata_c4",
+    "stomata_root_b_nonnegative", "vege_flux_cah2_small", "bare_flux_ehb2_small",
+    "frh2o_flerchinger", "phasechange_imelt_reset", "phasechange_below_supercool",
+    "combine_negative_snice", "combine_negative_soilice", "combine_middle_layer",
+    "combine_middle_layer_upper_neighbour", "snowh2o_nosnow_negative_soilice",
+    "snowh2o_thin_negative_soilice", "snowh2o_combine", "snowh2o_epore_small",
+    "snowwater_glacier_cap", "groundwater_table_above_layer3", "co2flux_rtmass_negative",
+    "sflx_unknown_opt_veg", "combine_negative_ponding", "sfcdif2_wstar2_zero_loop")
 NST, NSF, NSI, NFC, NDG = 56, 6, 6, 12, 58
 _libs = {}
 
@@ -51,19 +65,21 @@ def _lib(precision):
         if not available(precision):
             raise FileNotFoundError(f"{LIBS[precision]} missing (run make -C oracle port)")
         lib = C.CDLL(LIBS[precision])
-        rt = np.float64 if precision in (8, "8s") else np.float32
+        rt = np.float64 if precision in (8, "8s", "8b") else np.float32
         rp = np.ctypeslib.ndpointer(rt, flags="C_CONTIGUOUS")
         ip = np.ctypeslib.ndpointer(np.int32, flags="C_CONTIGUOUS")
-        creal = C.c_double if precision in (8, "8s") else C.c_float
+        creal = C.c_double if precision in (8, "8s", "8b") else C.c_float
         lib.oracle_sflx_batch.argtypes = [C.c_int32, creal, C.c_int32, creal, rp, rp, ip, rp, ip,
                                           rp, rp, ip, C.c_char_p, C.c_void_p]
         lib.oracle_sflx_run.argtypes = [C.c_int32, C.c_int32, creal, C.c_int32, creal, rp, rp, ip,
                                         rp, ip, rp, C.c_int32, rp, ip, C.c_char_p, C.c_void_p]
-        assert lib.oracle_real_bytes() == (8 if precision in (8, "8s") else 4)
+        assert lib.oracle_real_bytes() == (8 if precision in (8, "8s", "8b") else 4)
         if precision in ("4s", "8s"):
             lib.oracle_set_stats.argtypes = [C.c_void_p]
         if precision == "4d":
             lib.oracle_div_stats.argtypes = [C.c_void_p, C.c_int]
+        if precision in ("4b", "8b"):
+            lib.oracle_set_branches.argtypes = [C.c_void_p]
         _libs[precision] = (lib, rt)
     return _libs[precision]
 
@@ -104,6 +120,29 @@ def step_stats(P: dict, options, zsoil, dt, yearlen, julian, state, isnow, stati
     finally:
         lib.oracle_set_stats(None)
     return (*out, buf[:, :len(STAT_LOOPS)].copy())
+
+
+def step_branches(P: dict, options, zsoil, dt, yearlen, julian, state, isnow, static_f, static_i,
+                  forcing, precision=4):
+    """step() through the branch-marker build of `precision` (4 or 8): returns
+    step()'s tuple plus an (n,) uint32 mask, bit k set where the column
+    executed the branch BRANCH_SITES[k]."""
+    key = {4: "4b", 8: "8b"}[precision]
+    lib, _ = _lib(key)
+    mask = np.zeros(isnow.shape[0], np.uint32)
+    lib.oracle_set_branches(mask.ctypes.data)
+    try:
+        out = step(P, options, zsoil, dt, yearlen, julian, state, isnow, static_f, static_i,
+                   forcing, precision=key)
+    finally:
+        lib.oracle_set_branches(None)
+    return (*out, mask)
+
+
+def branch_hits(mask) -> dict:
+    """{site name: number of columns} of a step_branches mask."""
+    mask = np.asarray(mask, np.uint32)
+    return {name: int(((mask >> np.uint32(k)) & 1).sum()) for k, name in enumerate(BRANCH_SITES)}
 
 
 def div_stats(reset: bool = False) -> np.ndarray:

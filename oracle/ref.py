@@ -88,19 +88,21 @@ def _load():
     return _lib
 
 
-def configure(options: tuple, soil_tag: str = "STAS", veg_tag: str = "USGS"):
-    """Read the tables (from oracle/_ref/tbl, the reference reads the CWD) and set options."""
+def configure(options: tuple, soil_tag: str = "STAS", veg_tag: str = "USGS", tbl_dir: str = None):
+    """Read the tables (from oracle/_ref/tbl, the reference reads the CWD) and set options.
+    tbl_dir: another directory holding the three table files (an edited working copy)."""
     global _loaded_cfg
     lib = _load()
+    tbl_dir = TBL_DIR if tbl_dir is None else os.path.abspath(tbl_dir)
     with _lock:
-        if _loaded_cfg != (soil_tag, veg_tag):
+        if _loaded_cfg != (soil_tag, veg_tag, tbl_dir):
             cwd = os.getcwd()
-            os.chdir(TBL_DIR)
+            os.chdir(tbl_dir)
             try:
                 lib.ref_read_tables(soil_tag.encode(), len(soil_tag), veg_tag.encode(), len(veg_tag))
             finally:
                 os.chdir(cwd)
-            _loaded_cfg = (soil_tag, veg_tag)
+            _loaded_cfg = (soil_tag, veg_tag, tbl_dir)
         lib.ref_set_options(np.asarray(options, np.int32))
 
 

@@ -21,6 +21,12 @@ noahmp_amd.cases.  Each .npz holds inputs AND the reference outputs.
                                 that differs from the step-start ice fraction (compact's
                                 DDZ3, func.f90:5655)
 
+The physics branches these plausible-climate columns never take (snow caps,
+sign cases of the snow-layer bookkeeping, the C4 pathway, a water table inside
+the soil column, ...) have fixtures of their own, branch_base.npz,
+branch_veg2.npz, branch_combo.npz and branch_traj.npz, written by the
+neighbouring generator: python tests/golden/make_branch_golden.py
+
 usage (this container only; needs /root/reference):
   make -C oracle ref && python tests/golden/make_golden.py [group ...]
   groups: params single variants traj combos tables ficeold (default: all)

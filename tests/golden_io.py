@@ -24,6 +24,11 @@ def fixture_tags(g: dict) -> tuple[str, str]:
 
 
 def fixture_params(g: dict) -> dict:
+    """The table values a fixture was generated with: stored in the fixture
+    itself (param_<name> arrays) where the reference read an edited table,
+    else the dump of the shipped tables the fixture's tags name."""
+    if any(k.startswith("param_") for k in g):
+        return {k[6:]: (v if v.ndim else v[()]) for k, v in g.items() if k.startswith("param_")}
     soil, veg = fixture_tags(g)
     return load_params(veg, soil)
 
