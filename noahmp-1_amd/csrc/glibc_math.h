@@ -32,8 +32,10 @@
 
 #if defined(__HIPCC__) || defined(__HIP__)
 #define GM_HD __host__ __device__ __forceinline__
+#define GM_HDM __host__ __device__ __forceinline__
 #else
 #define GM_HD static inline
+#define GM_HDM inline
 #endif
 
 namespace gm {
@@ -479,6 +481,100 @@ GM_HD float atanf(float x) {
   z = hi - ((x * (s1 + s2) - lo) - x);
   return (hx & 0x80000000u) ? -z : z;
 }
+
+// ---- in-range cores ----------------------------------------------------------------
+// The main paths of expf / logf / powf / atanf alone: the same arithmetic in
+// the same order as the full functions above, without their special-case
+// exits.  Inside its interval each equals the full function (and so the host
+// libm) bit for bit (tests/test_glibc_math_inrange.py); outside it the result
+// is unspecified, but every table index stays masked, so any input, NaN
+// included, reads inside the tables.  The Newton loops call them where
+// tools/div_proof.py proves the argument's interval (sflx_math.h MthInRange32).
+
+// expf for finite |x| < 88: none of the overflow / underflow / inf / NaN exits
+GM_HD float expf_inrange(float x, const GmTables& T) {
+  const double InvLn2N = 0x1.71547652b82fep+0 * 32;
+  const double SHIFT = 0x1.8p+52;
+  const double C0 = 0x1.c6af84b912394p-5 / 32 / 32 / 32;
+  const double C1 = 0x1.ebfce50fac4f3p-3 / 32 / 32;
+  const double C2 = 0x1.62e42ff0c52d6p-1 / 32;
+  const double xd = (double)x;
+  const double z = InvLn2N * xd;
+  double kd = z + SHIFT;
+  const uint64_t ki = asuint64(kd);
+  kd -= SHIFT;
+  const double r = fma_(InvLn2N, xd, -kd);
+  uint64_t t = T.exp2f_tab[ki % 32];
+  t += ki << (52 - 5);
+  const double s = asdouble(t);
+  const double zz = fma_(C0, r, C1);
+  const double r2 = r * r;
+  double y = fma_(C2, r, 1.0);
+  y = fma_(zz, r2, y);
+  y = y * s;
+  return (float)y;
+}
+
+// logf for positive normal finite x, [2^-126, FLT_MAX]: x = 1 gives +0 through
+// the main path (i = 9: invc = 1, logc = 0, k = 0, r = 0), as the full
+// function's early return does
+GM_HD float logf_inrange(float x, const GmTables& T) {
+  const double Ln2 = 0x1.62e42fefa39efp-1;
+  const double A0 = -0x1.00ea348b88334p-2, A1 = 0x1.5575b0be00b6ap-2, A2 = -0x1.ffffef20a4123p-2;
+  const uint32_t OFF = 0x3f330000;
+  const uint32_t ix = asuint(x);
+  const uint32_t tmp = ix - OFF;
+  const int i = (tmp >> (23 - 4)) % 16;
+  const int k = (int32_t)tmp >> 23;
+  const uint32_t iz = ix - (tmp & 0x1ffu << 23);
+  const double invc = T.logf_tab[2 * i], logc = T.logf_tab[2 * i + 1];
+  const double z = (double)asfloat(iz);
+  const double r = fma_(z, invc, -1.0);
+  const double y0 = fma_((double)k, Ln2, logc);
+  const double r2 = r * r;
+  double y = fma_(A1, r, A2);
+  y = fma_(A0, r2, y);
+  y = fma_(y, r2, y0 + r);
+  return (float)y;
+}
+
+// powf(x, y) for positive normal finite x, finite nonzero y and
+// |y * log2(x)| < 126: no special-case block, no overflow / underflow exit
+GM_HD float powf_inrange(float x, float y, const GmTables& T) {
+  return powf_exp2((double)y * powf_log2(asuint(x), T), 0, T);
+}
+
+// atanf for 1 <= x < 2^25: fdlibm's three cases of that interval chosen by
+// its own breakpoints (19/16 and 39/16) as selects of the numerator, the
+// denominator, hi and lo, then one division `div(num, den)` and the
+// polynomial.  den >= 1; num is -1, 0 or 2^-23 <= |num| < 1.  `div` must
+// return the IEEE quotient num / den.
+template <class Div>
+GM_HD float atanf_ge1(float x, Div div) {
+  const float atanhi1 = 7.8539812565e-01f, atanhi2 = 9.8279368877e-01f;
+  const float atanhi3 = 1.5707962513e+00f;
+  const float atanlo1 = 3.7748947079e-08f, atanlo2 = 3.4473217170e-08f;
+  const float atanlo3 = 7.5497894159e-08f;
+  const float aT0 = 3.3333334327e-01f, aT1 = -2.0000000298e-01f, aT2 = 1.4285714924e-01f;
+  const float aT3 = -1.1111110449e-01f, aT4 = 9.0908870101e-02f, aT5 = -7.6918758452e-02f;
+  const float aT6 = 6.6610731184e-02f, aT7 = -5.8335702866e-02f, aT8 = 4.9768779427e-02f;
+  const float aT9 = -3.6531571299e-02f, aT10 = 1.6285819933e-02f;
+  const uint32_t ix = asuint(x);
+  const bool c1 = ix < 0x3f980000u, c2 = ix < 0x401c0000u;
+  const float num = c1 ? x - 1.0f : c2 ? x - 1.5f : -1.0f;
+  const float den = c1 ? x + 1.0f : c2 ? 1.0f + 1.5f * x : x;
+  const float hi = c1 ? atanhi1 : c2 ? atanhi2 : atanhi3;
+  const float lo = c1 ? atanlo1 : c2 ? atanlo2 : atanlo3;
+  const float t = div(num, den);
+  const float z = t * t;
+  const float w = z * z;
+  const float s1 = z * (aT0 + w * (aT2 + w * (aT4 + w * (aT6 + w * (aT8 + w * aT10)))));
+  const float s2 = w * (aT1 + w * (aT3 + w * (aT5 + w * (aT7 + w * aT9))));
+  return hi - ((t * (s1 + s2) - lo) - t);
+}
+struct DivIeee {
+  GM_HDM float operator()(float a, float b) const { return a / b; }
+};
 
 // ---- log10f (fdlibm float, calls the ARM logf) ----------------------------------
 GM_HD float log10f(float x, const GmTables& T) {

@@ -228,11 +228,18 @@ DEV Sfc1Inv<T> sfc1_inv(D& d, T sfctmp, T qair, T rhoair, T zlvl, T zpd, T z0h) 
   return v;
 }
 
+// The libm calls (pow_q, log, atan) go through the loop's math policy
+// (sflx_math.h LoopMth): with DivFast32 the in-range cores, whose arguments
+// 1 - 16*MOZ and 1 - 16*MOZ2 are finite and below 2^100 when MOZ and MOZ2 are
+// >= NMP_DOM_MOZ_LO.  Returns that window's verdict (true under DivRef): the
+// caller folds it into the lane's `ok`.  MIN(., 1) maps a NaN quotient to 1,
+// so neither is NaN.
 template <class T, bool R, class D>
-DEV void sfcdif1(D& d, const Sfc1Inv<T>& inv, int iter, T h, const Sfc1Logs<T, R>& lg, T ur,
+DEV bool sfcdif1(D& d, const Sfc1Inv<T>& inv, int iter, T h, const Sfc1Logs<T, R>& lg, T ur,
                  T mpe, T& moz, int& mozsgn, T& fm, T& fh, T& fm2, T& fh2, T& cm, T& ch, T& fv,
                  bool two_m) {
-  typedef Mth<T, R> M;
+  typedef typename LoopMth<T, R, D>::type M;
+  constexpr bool kInRange = !std::is_same<M, Mth<T, R>>::value;
   T mozold = moz;
   const T tmpcm = lg.tmpcm, tmpch = lg.tmpch, tmpcm2 = lg.tmpcm2, tmpch2 = lg.tmpch2;
   T moz2;
@@ -259,6 +266,8 @@ DEV void sfcdif1(D& d, const Sfc1Inv<T>& inv, int iter, T h, const Sfc1Logs<T, R
     fm2 = L(0.0);
     fh2 = L(0.0);
   }
+  bool win = true;
+  if constexpr (kInRange) win = (moz >= (T)NMP_DOM_MOZ_LO) & (moz2 >= (T)NMP_DOM_MOZ_LO);
   T fmnew, fhnew, fm2new, fh2new;
   if (moz < L(0.0)) {
     T tmp1 = M::pow_q(L(1.0) - L(16.0) * moz);
@@ -307,6 +316,7 @@ DEV void sfcdif1(D& d, const Sfc1Inv<T>& inv, int iter, T h, const Sfc1Logs<T, R
   cm = d.divk(KARMAN * KARMAN, d.rec(cmfm * cmfm));
   ch = d.divk(KARMAN * KARMAN, d.rec(cmfm * chfh));
   fv = ur * d.sqrt(cm);  // CM in the proof's interval (tools/div_proof.py)
+  return win;
 }
 
 // sfcdif2 (Chen97, opt_sfc=2): func.f90:3511-3689
@@ -390,11 +400,16 @@ DEV void sfcdif2(int iter, T z0, T thz0, T thlm, T sfcspd, T czil, T zlm, T& akm
 
 // rhocp = d.rec(RHOAIR*CPAIR), rhcan = d.rec(HCAN) and dzg = ZPD-Z0MG
 // (d.chk) are loop-invariant and formed once by the caller.
+// The libm calls (pow_mq, four exp) go through the loop's math policy as in
+// sfcdif1; returns the verdict of the window MOZG >= NMP_DOM_MOZG_LO, which
+// keeps 1 - 15*MOZG finite and below 2^100.  The four exp arguments lie in
+// [-2 CWPC, CWPC] with CWPC <= 17 by the range proof.
 template <class T, bool R, class D>
-DEV void ragrb(D& d, const Recip<T>& rhocp, const Recip<T>& rhcan, T dzg, T sqrt_dleaf_uc,
+DEV bool ragrb(D& d, const Recip<T>& rhocp, const Recip<T>& rhcan, T dzg, T sqrt_dleaf_uc,
                int iter, T vai, T hg, T tah, T zpd, T z0hg, T hcan, T z0h, T fv, T cwp, T mpe,
                T& fhg, T& rahg, T& rb) {
-  typedef Mth<T, R> M;
+  typedef typename LoopMth<T, R, D>::type M;
+  constexpr bool kInRange = !std::is_same<M, Mth<T, R>>::value;
   T mozg = L(0.0);
   if (iter > 1) {
     T tmp1 = d.div(KARMAN * d.divk(GRAV, d.rec(tah)) * hg, rhocp);
@@ -412,6 +427,8 @@ DEV void ragrb(D& d, const Recip<T>& rhocp, const Recip<T>& rhcan, T dzg, T sqrt
   rahg = d.div(tmprah2, d.rec(kh));
   T tmprb = d.div(cwpc * L(50.0), d.rec(L(1.0) - M::exp(-cwpc / L(2.0))));
   rb = tmprb * sqrt_dleaf_uc;
+  if constexpr (kInRange) return mozg >= (T)NMP_DOM_MOZG_LO;
+  return true;
 }
 
 // stomata (Ball-Berry bisection): func.f90:3739-3887
@@ -969,7 +986,7 @@ static __device__ unsigned int nmp_wave_ctr;
 #endif
 #ifdef NMP_COUNT_FALLBACK
 static __device__ unsigned int nmp_fallback_ctr;
-static __device__ unsigned int nmp_fb_reason[32];
+static __device__ unsigned int nmp_fb_reason[64];
 #endif
 
 
@@ -1345,12 +1362,12 @@ DEV void sflx_column(const DevParams& P, const KArgs<T>& A, Col<T>& c, const Sin
   NMP_PHASE(4);
 #ifdef NMP_COUNT_FALLBACK
   // (probe builds) which condition sent the lane to an IEEE loop
-  unsigned fb_why = 0;
+  unsigned long long fb_why = 0;
 #define NMP_DOM(flag, bit, cond)                 \
   do {                                           \
     const bool c_ = (cond);                      \
     flag = flag & c_;                            \
-    if (!c_) fb_why |= 1u << (bit);              \
+    if (!c_) fb_why |= 1ull << (bit);            \
   } while (0)
 #else
 #define NMP_DOM(flag, bit, cond) flag = flag & (bool)(cond)
@@ -1463,9 +1480,11 @@ DEV void sflx_column(const DevParams& P, const KArgs<T>& A, Col<T>& c, const Sin
       // iterations carries none of stomata's code or registers.
       auto vege_iter = [&](const int iter, auto first) -> T {
         if constexpr (!decltype(first)::value) __builtin_assume(iter >= 2);
-        if (o.sfc == 1)
-          sfcdif1<T, R>(d, inv, iter, h, lgv, ur, mpe, moz, mozsgn, fm, fh, fm2, fh2, cmv, chv, fv,
-                        diag_on);
+        if (o.sfc == 1) {
+          const bool w = sfcdif1<T, R>(d, inv, iter, h, lgv, ur, mpe, moz, mozsgn, fm, fh, fm2, fh2,
+                                       cmv, chv, fv, diag_on);
+          if constexpr (kFast) NMP_DOM(ok, 32, w);
+        }
         if (o.sfc == 2) {
           sfcdif2<T, R>(iter, z0m, c.tah, thair, ur, (T)P.g.czil, zlvl, cmv, chv, moz, wstar, fv);
           chv = chv / ur;
@@ -1473,8 +1492,9 @@ DEV void sflx_column(const DevParams& P, const KArgs<T>& A, Col<T>& c, const Sin
         }
         rahc = rmax(L(1.0), d.divk(L(1.0), d.rec(chv * ur)));
         const Recip<T> rrahc = d.rec(rahc);  // RAWC = RAHC: CAH = CAW, H share it
-        ragrb<T, R>(d, inv.rhocp, rhcan, dzg, sqrt_dleaf_uc, iter, vaie, hg, c.tah, zpd, z0mg, hcan,
-                    z0h, fv, cwp, mpe, fhg, rahg, rb);
+        const bool wg = ragrb<T, R>(d, inv.rhocp, rhcan, dzg, sqrt_dleaf_uc, iter, vaie, hg, c.tah,
+                                    zpd, z0mg, hcan, z0h, fv, cwp, mpe, fhg, rahg, rb);
+        if constexpr (kFast) NMP_DOM(ok, 33, wg);
         if constexpr (kFast) NMP_DOM(ok, 16, in(rahg, (T)NMP_DOM_RAHG_LO, (T)NMP_DOM_RAHG_HI));
         const Recip<T> rrahg = d.rec(rahg), rrb = d.rec(rb);  // RAWG = RAHG
         T estv, destv;
@@ -1592,8 +1612,8 @@ DEV void sflx_column(const DevParams& P, const KArgs<T>& A, Col<T>& c, const Sin
       if (!vege_domain_ok() || !vege_loop(df)) {
 #ifdef NMP_COUNT_FALLBACK
         atomicAdd(&nmp_fallback_ctr, 1u);
-        for (int b = 0; b < 29; ++b)
-          if ((0x1c0fffffu >> b) & (fb_why >> b) & 1u) atomicAdd(&nmp_fb_reason[b], 1u);
+        for (int b = 0; b < 34; ++b)
+          if ((0x31c0fffffull >> b) & (fb_why >> b) & 1u) atomicAdd(&nmp_fb_reason[b], 1u);
 #endif
         c.tv = out.ls(NMP_S_TV);
         c.tah = out.ls(NMP_S_TAH);
@@ -1695,9 +1715,11 @@ DEV void sflx_column(const DevParams& P, const KArgs<T>& A, Col<T>& c, const Sin
 #pragma unroll sizeof(T) == 4 ? 5 : 1
       for (int iter = 1; iter <= 5; ++iter) {
         if constexpr (kFast) NMP_DOM(ok, 20, in(tgb, (T)NMP_DOM_T_LO, (T)NMP_DOM_TGB_HI));
-        if (o.sfc == 1)
-          sfcdif1<T, R>(d, invb, iter, h, lgb, ur, mpe, moz, mozsgn, fm, fh, fm2, fh2, cmb, chb, fv,
-                        diag_on);
+        if (o.sfc == 1) {
+          const bool w = sfcdif1<T, R>(d, invb, iter, h, lgb, ur, mpe, moz, mozsgn, fm, fh, fm2, fh2,
+                                       cmb, chb, fv, diag_on);
+          if constexpr (kFast) NMP_DOM(ok, 34, w);
+        }
         if (o.sfc == 2) {
           sfcdif2<T, R>(iter, z0mg, tgb, thair, ur, (T)P.g.czil, zlvl, cmb, chb, moz, wstar, fv);
           chb = chb / ur;
@@ -1757,8 +1779,8 @@ DEV void sflx_column(const DevParams& P, const KArgs<T>& A, Col<T>& c, const Sin
       if (!bare_domain_ok() || !bare_loop(dfb)) {
 #ifdef NMP_COUNT_FALLBACK
         atomicAdd(&nmp_fallback_ctr, 1u);
-        for (int b = 20; b < 31; ++b)
-          if ((0x60f00000u >> b) & (fb_why >> b) & 1u) atomicAdd(&nmp_fb_reason[b], 1u);
+        for (int b = 20; b < 35; ++b)
+          if ((0x460f00000ull >> b) & (fb_why >> b) & 1u) atomicAdd(&nmp_fb_reason[b], 1u);
 #endif
         bare_loop(drb);
       }
@@ -3263,12 +3285,20 @@ extern "C" long long nmp_debug_fallback_count(int reset, unsigned int* why32) {
                    hipSuccess)
     return -4;
   if (reset) {
-    const unsigned int z[32] = {0};
+    const unsigned int z[64] = {0};
     if (hipMemcpyToSymbol(HIP_SYMBOL(nmp_fallback_ctr), z, sizeof(unsigned int)) != hipSuccess ||
         hipMemcpyToSymbol(HIP_SYMBOL(nmp_fb_reason), z, sizeof(z)) != hipSuccess)
       return -4;
   }
   return n;
+}
+// all 64 reason counters (the first 32 are nmp_debug_fallback_count's; 32..34
+// are the libm windows on MOZ/MOZ2, MOZG and the bare loop's MOZ/MOZ2)
+extern "C" int nmp_debug_fallback_reasons(unsigned int* why64) {
+  return hipMemcpyFromSymbol(why64, HIP_SYMBOL(nmp_fb_reason), 64 * sizeof(unsigned int)) ==
+                 hipSuccess
+             ? 0
+             : -4;
 }
 #endif
 

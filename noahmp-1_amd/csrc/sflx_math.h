@@ -255,6 +255,37 @@ struct DivFast32 {
   __device__ __forceinline__ static float sqrt(float x) { return sqrt_normal32(x); }
 };
 
+// One math policy per division policy (sfcdif1 and ragrb, the libm callers of
+// the Newton loops).  With DivRef the loops call the full functions of Mth.
+// With DivFast32 they call the in-range cores of glibc_math.h: the same main
+// paths without the special-case exits, so an inlined call is straight-line
+// code with no exec-mask branch.  tools/div_proof.py ("libm sites") derives
+// every argument's interval from the domain of vege_domain.h and its windows
+// on MOZ, MOZ2 and MOZG; a lane outside them re-runs its loop with DivRef and
+// the full functions.  atanf's one division has a denominator >= 1 and a
+// numerator that is -1, 0 or in [2^-23, 1): inside DivFast32's exact region.
+template <class T, bool R, class D>
+struct LoopMth {
+  typedef Mth<T, R> type;
+};
+struct MthInRange32 : Mth<float, true> {
+  NMP_MATH_FN float exp(float x) { return gm::expf_inrange(x, gm_lds); }
+  NMP_MATH_FN float log(float x) { return gm::logf_inrange(x, gm_lds); }
+  NMP_MATH_FN float pow_q(float x) { return gm::powf_inrange(x, 0.25f, gm_lds); }
+  NMP_MATH_FN float pow_mq(float x) { return gm::powf_inrange(x, -0.25f, gm_lds); }
+  struct Div {
+    __device__ __forceinline__ float operator()(float a, float b) const {
+      const DivFast32 d;
+      return d.div(a, d.rec(b));
+    }
+  };
+  NMP_MATH_FN float atan(float x) { return gm::atanf_ge1(x, Div{}); }
+};
+template <>
+struct LoopMth<float, true, DivFast32> {
+  typedef MthInRange32 type;
+};
+
 // Register-array access with a runtime index, lowered to a select chain so the
 // array itself stays in VGPRs (a dynamic subscript would demote it to scratch).
 // The empty asm pins each element as a register value: without it InstCombine

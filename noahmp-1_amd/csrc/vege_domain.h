@@ -13,6 +13,20 @@
 // the loop from its start with IEEE division, so its results are the
 // reference's bits either way.  tools/div_proof.py reads this file: it is the
 // one copy of the numbers.
+//
+// The same domain carries the loops' libm calls.  Under DivFast32, sfcdif1 and
+// ragrb call the in-range cores of glibc_math.h (sflx_math.h MthInRange32):
+// expf for |x| < 88, logf and powf(x, +-0.25) for positive normal finite x,
+// atanf for 1 <= x < 2^25.  tools/div_proof.py ("libm sites") derives each
+// argument's interval: the four expf arguments lie in [-2 CWPC, CWPC] with
+// CWPC <= 17; the others come from 1 - 16 MOZ, 1 - 16 MOZ2 and 1 - 15 MOZG,
+// evaluated only where the stability parameter is negative, so they are >= 1,
+// and below 2^100 by the windows MOZ_LO and MOZG_LO at the end of the first
+// part of this file, checked per lane in every iteration.  No argument can be
+// NaN: MOZ, MOZ2 and MOZG are MIN(quotient, 1), which maps NaN to 1, and a NaN
+// FHG needs a NaN MOZG; a NaN TAH, H or HG comes from a NaN temperature,
+// which fails the windows on TV and TGB.  The full functions stay in the
+// DivRef loops and everywhere else.
 #pragma once
 
 // air, ground and canopy temperatures (K); TV at the start of every iteration
@@ -139,6 +153,19 @@
 #endif
 #ifndef NMP_DOM_CGH_HI
 #define NMP_DOM_CGH_HI 1.0e6
+#endif
+// The stability parameters MOZ, MOZ2 (sfcdif1, both loops) and MOZG (ragrb):
+// each is MIN(quotient, 1), checked per lane in every iteration to be >= the
+// limit below.  The range proof bounds them statically (|MOZ| <= 3.5e12,
+// |MOZG| <= 3.9e13 inside the domain above) through the induction over the
+// loop-carried values; the windows make the libm cores' argument intervals
+// hold without it: 1 + 16e16 < 2^100 keeps powf's |y log2 x| below 126 and
+// logf's argument finite, and (1.6e17)^0.25 < 2^25 is atanf's upper bound.
+#ifndef NMP_DOM_MOZ_LO
+#define NMP_DOM_MOZ_LO -1.0e16
+#endif
+#ifndef NMP_DOM_MOZG_LO
+#define NMP_DOM_MOZG_LO -1.0e16
 #endif
 
 // ---- the stomata bisection (stomata, func.f90:3739-3887; sflx_kernel.hip

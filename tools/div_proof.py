@@ -27,6 +27,26 @@ an iteration starts from (TV, TAH, H, HG, FV, FHG, MOZ/FM/FH) are assumed in
 the intervals below, the iteration is shown to end inside them again; TV and
 RAHG are the two the kernel checks at run time, every iteration.
 
+The same domain carries the loops' libm calls ("libm sites", below the
+division table).  Under DivFast32, sfcdif1 and ragrb call the in-range cores of
+csrc/glibc_math.h, each the full function's main path and equal to it inside
+
+  expf_inrange   |x| < 88
+  logf_inrange   2^-126 <= x <= FLT_MAX
+  powf_inrange   2^-126 <= x <= FLT_MAX and |y log2 x| < 126
+  atanf_ge1      1 <= x < 2^25
+
+For every call the argument's signed interval is derived and checked against
+these.  The expf arguments follow from CWPC's interval above.  The others
+come from 1 - 16 MOZ, 1 - 16 MOZ2 and 1 - 15 MOZG, evaluated only where the
+stability parameter is negative (so they are >= 1) and bounded above by the
+per-lane windows MOZ_LO and MOZG_LO of vege_domain.h; the static bounds of
+the division table (which rest on the induction over the loop-carried values)
+are shown to lie inside the windows, so a lane inside the static domain never
+leaves through them.  None can be NaN: MOZ, MOZ2 and MOZG are MIN(quotient, 1),
+which maps NaN to 1 (a < b ? a : b), -inf fails the window, and FHG is an
+average of values in (0, 5.7].
+
     python tools/div_proof.py            # prints the per-site table, exit 1 on a failure
 """
 import math
@@ -112,6 +132,64 @@ def sqrt_site(name, x, ref, note=""):
                  ("sqrt: " + note) if note else "sqrt"))
     if not ok:
         bad.append(name)
+
+
+FLT_MAX = 3.4028234e38
+libm_rows = []
+
+
+def libm_site(name, func, lo, hi, ref, y=None, note="", lo_exact=False):
+    """Record one libm call whose argument lies in [lo, hi] (signed; widened by
+    W here) against the interval of its in-range core (glibc_math.h).
+    lo_exact: the lower bound is a floor the fp32 arithmetic keeps exactly
+    (1 - 16 MOZ >= 1 for MOZ < 0; powf(x >= 1, 0.25) >= 1, which
+    tests/native/glibc_math_inrange_check.cpp checks with pow_q; (1 + t) / 2 >= 1
+    for t >= 1), not widened."""
+    lo, hi = lo if lo_exact else lo - abs(lo) * W, hi + abs(hi) * W
+    if func == "expf":
+        ok = -88.0 < lo and hi < 88.0
+    elif func == "logf":
+        ok = N_MIN <= lo and hi <= FLT_MAX
+    elif func == "powf":
+        ok = N_MIN <= lo and hi <= FLT_MAX and \
+            max(abs(y * math.log2(lo)), abs(y * math.log2(hi))) < 126.0
+    elif func == "atanf":
+        ok = 1.0 <= lo and hi < 2.0 ** 25
+    else:
+        raise ValueError(func)
+    libm_rows.append((name, func, ref, lo, hi, ok, note))
+    if not ok:
+        bad.append(name)
+
+
+def libm_sites(D, moz_static, moz2_static, mozg_static, cwpc, q14, q15):
+    """The libm calls of sfcdif1 (:3443-3452, both loops and, on output steps,
+    the 2-m chain) and ragrb (:3320, :3334-3346) under DivFast32."""
+    moz_w, mozg_w = -D["MOZ_LO"], -D["MOZG_LO"]     # the windows: MOZ >= MOZ_LO < 0
+    assert moz_w > 0 and mozg_w > 0
+    # inside the static domain the windows never fire
+    assert moz_static <= moz_w and moz2_static <= moz_w and mozg_static <= mozg_w, \
+        (moz_static, moz2_static, mozg_static)
+    for tag, lim in (("MOZ", moz_w), ("MOZ2", moz_w)):
+        x_hi = 1.0 + 16.0 * lim                      # 1 - 16 MOZ, MOZ in [MOZ_LO, 0)
+        libm_site(f"libm: ({tag}) TMP1 = (1 - 16 {tag})**0.25", "powf", 1.0, x_hi, ":3443",
+                  y=0.25, lo_exact=True, note=f"{tag} < 0 here and >= MOZ_LO (window, every iteration)")
+        t_hi = x_hi ** 0.25 * (1 + 2.0 ** -22)       # powf is within 1 ulp
+        libm_site(f"libm: ({tag}) LOG((1 + TMP1**2) / 2)", "logf", 1.0, (1.0 + t_hi * t_hi) / 2,
+                  ":3444", lo_exact=True, note="TMP1 >= 1: powf(x >= 1, 0.25) >= 1")
+        libm_site(f"libm: ({tag}) LOG((1 + TMP1) / 2)", "logf", 1.0, (1.0 + t_hi) / 2, ":3445",
+                  lo_exact=True)
+        libm_site(f"libm: ({tag}) ATAN(TMP1)", "atanf", 1.0, t_hi, ":3446",
+                  lo_exact=True, note="one division num / den: den >= 1, num -1, 0 or in [2^-23, 1)")
+    libm_site("libm: FHGNEW = (1 - 15 MOZG)**(-0.25)", "powf", 1.0, 1.0 + 15.0 * mozg_w, ":3320",
+              y=-0.25, lo_exact=True, note="MOZG < 0 here and >= MOZG_LO (window, every iteration)")
+    libm_site("libm: EXP(-CWPC*Z0HG / HCAN)", "expf", -q14.hi, 0.0, ":3334")
+    libm_site("libm: EXP(-CWPC*(Z0H+ZPD) / HCAN)", "expf", -q15.hi, 0.0, ":3335")
+    libm_site("libm: EXP(CWPC)", "expf", cwpc.lo, cwpc.hi, ":3336")
+    libm_site("libm: EXP(-CWPC / 2)", "expf", -cwpc.hi / 2, -cwpc.lo / 2, ":3346")
+    # atanf_ge1's division through DivFast32 (sflx_math.h MthInRange32::Div)
+    site("libm: ATAN's NUM / DEN", M(2.0 ** -23, 1.0, True), M(1.0, 2.0 ** 26), "atanf",
+         "den = x+1, 1+1.5x or x; num = x-1, x-1.5 (multiples of 2^-23) or -1")
 
 
 def esat_range():
@@ -283,8 +361,8 @@ def main():
     tmp1 = M(1e-6, tmp1.hi)                         # IF (ABS(TMP1) <= MPE) TMP1 = MPE
     fv3 = fn(lambda x: x ** 3, fv)
     mol = site("MOL = -FV**3 / TMP1", fv3, tmp1, ":3433")
-    site("MOZ = (ZLVL-ZPD) / MOL", dz, mol, ":3434", "then MIN(., 1)")
-    site("MOZ2 = (2+Z0H) / MOL", d2, mol, ":3435", "then MIN(., 1)")
+    moz_q = site("MOZ = (ZLVL-ZPD) / MOL", dz, mol, ":3434", "then MIN(., 1)")
+    moz2_q = site("MOZ2 = (2+Z0H) / MOL", d2, mol, ":3435", "then MIN(., 1)")
     cm_q = site("CM = KARMAN**2 / CMFM**2", c(0.16), cmfm * cmfm, ":3499",
                 "CMFM >= 0.1 TMPCM: FM <= 0.9 TMPCM (:3455)")
     site("CH = KARMAN**2 / (CMFM*CHFH)", c(0.16), cmfm * cmfm, ":3500")
@@ -398,6 +476,7 @@ def main():
 
     stomata_sites(D, T, p, es, rb)
     soil_sites()
+    libm_sites(D, moz_q.hi, moz2_q.hi, mozg.hi, cwpc, q14, q15)
 
     # ---- induction: the iteration ends inside the intervals it started from ----
     assert h_q.hi <= h.hi * 1.001 and h_q.lo >= h.lo * 0.999, (h_q, h)
@@ -414,9 +493,18 @@ def main():
               + (f"  ({note})" if note else ""))
     print(f"derived: FHG >= {fhg_lo:.3g}, CWPC in {cwpc!r}, FV in {fv!r}, RAHC in {rahc!r}, "
           f"RB in {rb!r}")
+    print("libm sites (in-range cores, csrc/glibc_math.h): expf |x| < 88; logf, powf x in "
+          "[2^-126, FLT_MAX], |y log2 x| < 126; atanf x in [1, 2^25)")
+    print(f"libm windows: MOZ_LO = {D['MOZ_LO']:.17g}, MOZG_LO = {D['MOZG_LO']:.17g} "
+          f"(static: |MOZ| <= {moz_q.hi:.3g}, |MOZ2| <= {moz2_q.hi:.3g}, |MOZG| <= {mozg.hi:.3g})")
+    print(f"{'site':46s} {'func.f90':8s} {'core':6s} {'argument in':>30s}  ok")
+    for name, func, ref, lo, hi, ok, note in libm_rows:
+        print(f"{name:46s} {ref:8s} {func:6s} {f'[{lo:.6g}, {hi:.6g}]':>30s}  "
+              f"{'yes' if ok else 'NO'}" + (f"  ({note})" if note else ""))
     if bad:
         print("FAILED:", bad)
         return 1
+    print(f"all {len(libm_rows)} libm sites inside their cores' intervals")
     print(f"all {len(rows)} sites inside the exact region")
     return 0
 

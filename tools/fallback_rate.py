@@ -36,7 +36,11 @@ def main():
                  22: "bare: TMPCM..", 23: "bare: heights/RSURF", 24: "stomata on IEEE",
                  25: "soil-water division on IEEE", 15: "EMG", 26: "CTR numerator",
                  27: "TR numerator", 28: "DTV numerator", 29: "bare: DTG numerator",
-                 30: "bare: EMG/CGH"}
+                 30: "bare: EMG/CGH", 32: "libm: MOZ/MOZ2 window", 33: "libm: MOZG window",
+                 34: "bare: libm MOZ/MOZ2 window"}
+    more = hasattr(raw, "nmp_debug_fallback_reasons")  # 64 counters (libm windows: 32..34)
+    if more:
+        raw.nmp_debug_fallback_reasons.argtypes = [C.c_void_p]
     for kind, n, opt_veg, nsteps in (("mixed", 1 << 20, 1, 25), ("conus", 1 << 20, 1, 25),
                                      ("global", 1_036_800, 2, 25), ("casenml", 65536, 1, 96)):
         eng = Engine(P, dict(L.CASE_NML_OPTIONS, opt_veg=opt_veg), device=0)
@@ -52,12 +56,14 @@ def main():
             sh.step(f, cases.CASE_NML_ZSOIL, 1800.0, jul, 366)
         sh.join()
         torch.cuda.synchronize()
-        why = np.zeros(32, np.uint32)
-        fb = raw.nmp_debug_fallback_count(1, why.ctypes.data)
+        why = np.zeros(64, np.uint32)
+        if more:
+            raw.nmp_debug_fallback_reasons(why.ctypes.data)
+        fb = raw.nmp_debug_fallback_count(1, None if more else why.ctypes.data)
         print(f"{kind:8s} {n:8d} columns x {nsteps} steps: {fb} IEEE loop re-runs (canopy + bare) "
               f"({fb / (n * nsteps):.2e} per column-step), status bits "
               f"{int((cs.status != 0).sum())}", flush=True)
-        print("   by condition:", {why_names.get(b, b): int(why[b]) for b in range(32) if why[b]},
+        print("   by condition:", {why_names.get(b, b): int(why[b]) for b in range(64) if why[b]},
               flush=True)
         eng.close()
 
