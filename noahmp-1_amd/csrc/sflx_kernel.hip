@@ -189,18 +189,25 @@ DEV void twostream_all(const DevParams& P, const VegRec& V, const Opt& o, T cosz
 // sfcdif1: func.f90:3353-3508
 // The four log terms of sfcdif1 (:3417-3420) depend only on heights fixed for
 // the whole Newton loop; callers evaluate them once (same values, bit for bit)
-// instead of once per iteration as the reference does.
+// instead of once per iteration as the reference does.  TwoM false_type (a
+// kernel compiled for steps that write no diagnostics): the 2-m height's pair,
+// which feeds only the 2-m diagnostics, is not formed.
 template <class T, bool R>
 struct Sfc1Logs {
   T tmpcm, tmpch, tmpcm2, tmpch2;
   DEV Sfc1Logs() : tmpcm(0), tmpch(0), tmpcm2(0), tmpch2(0) {}
-  DEV Sfc1Logs(T zlvl, T zpd, T z0m, T z0h, int& status, const T* log_2z0m = nullptr) {
+  template <class TwoM>
+  DEV Sfc1Logs(TwoM, T zlvl, T zpd, T z0m, T z0h, int& status, const T* log_2z0m = nullptr) {
     typedef Mth<T, R> M;
     if (zlvl <= zpd) status |= NMP_ST_ZLVL;  // :3412-3415
     tmpcm = M::log((zlvl - zpd) / z0m);
     tmpch = (z0h == z0m) ? tmpcm : M::log((zlvl - zpd) / z0h);
-    tmpcm2 = log_2z0m ? *log_2z0m : M::log((L(2.0) + z0m) / z0m);
-    tmpch2 = (z0h == z0m) ? tmpcm2 : M::log((L(2.0) + z0h) / z0h);
+    if constexpr (TwoM::value) {
+      tmpcm2 = log_2z0m ? *log_2z0m : M::log((L(2.0) + z0m) / z0m);
+      tmpch2 = (z0h == z0m) ? tmpcm2 : M::log((L(2.0) + z0h) / z0h);
+    } else {
+      tmpcm2 = tmpch2 = L(0.0);
+    }
   }
 };
 
@@ -1000,7 +1007,11 @@ constexpr Opt kOptionSet[3] = {{1, 1, 1, 1, 1, 1, 1, 1, 2, 1, 1, 1},
                                {1, 1, 1, 1, 1, 1, 1, 1, 2, 1, 1, 1},
                                {2, 1, 1, 1, 1, 1, 1, 1, 2, 1, 1, 1}};
 
-template <class T, bool R, int OS>
+// DIAG false: the step compiled for launches that write no diagnostics
+// (Sink::level the constant NMP_DIAG_NONE): the 2-m chain, TRAD and every other
+// diagnostic-only value have no code and hold no register.  The state it
+// leaves is the DIAG kernel's, bit for bit: nothing prognostic reads them.
+template <class T, bool R, int OS, bool DIAG>
 DEV void sflx_column(const DevParams& P, const KArgs<T>& A, Col<T>& c, const Sink<T>& out) {
   typedef Mth<T, R> M;
 
@@ -1112,7 +1123,7 @@ DEV void sflx_column(const DevParams& P, const KArgs<T>& A, Col<T>& c, const Sin
   T t2mv = 0, q2v = 0, chv = 0, chleaf = 0, chuc = 0, chv2 = 0, rssun = 0, rssha = 0;
   // the diagnostic-only chains (the 2-m MOZ2 -> FH2 -> CHV2/CHB2 -> T2M, Q2;
   // TRAD) only when the step writes diagnostics: nothing else reads them
-  const bool diag_on = out.level != NMP_DIAG_NONE;
+  const bool diag_on = DIAG && out.level != NMP_DIAG_NONE;
   T bgap = 0, wgap = 0;
   T ur = rmax(M::sqrt(c.uu * c.uu + c.vv * c.vv), L(1.0));
   T vai = elai + esai;
@@ -1396,7 +1407,8 @@ DEV void sflx_column(const DevParams& P, const KArgs<T>& A, Col<T>& c, const Sin
     T sqrt_dleaf_uc = M::sqrt((T)V.dleaf / uc);  // ragrb :3349, loop-invariant
     const T log_2z0m_v = (T)V.log_2z0m;  // Z0M = Z0MVT: veg-type-only
     Sfc1Logs<T, R> lgv =
-        (o.sfc == 1) ? Sfc1Logs<T, R>(zlvl, zpd, z0m, z0h, c.status,
+        (o.sfc == 1) ? Sfc1Logs<T, R>(std::bool_constant<DIAG>{}, zlvl, zpd, z0m, z0h,
+                                      c.status,
                                       (sizeof(T) == 4 && R) ? &log_2z0m_v : nullptr)
                      : Sfc1Logs<T, R>{};
     // EVC's limit CANLIQ*LATHEAV/DT or CANICE*LATHEAV/DT (:2860-2864): both
@@ -1413,10 +1425,13 @@ DEV void sflx_column(const DevParams& P, const KArgs<T>& A, Col<T>& c, const Sin
       NMP_DOM(k, 1, in(qair, 0.0, 1.0) & in(rhoair, NMP_DOM_RHO_LO, NMP_DOM_RHO_HI));
       NMP_DOM(k, 2, in(c.sfcprs, NMP_DOM_P_LO, NMP_DOM_P_HI) & in(eair, 0.0, NMP_DOM_EAIR_HI));
       NMP_DOM(k, 3, in(ur, 1.0, NMP_DOM_UR_HI));
-      NMP_DOM(k, 4, in(lgv.tmpcm, NMP_DOM_TMPC_LO, NMP_DOM_TMPC_HI) &
-                        in(lgv.tmpch, NMP_DOM_TMPC_LO, NMP_DOM_TMPC_HI) &
-                        in(lgv.tmpcm2, NMP_DOM_TMPC_LO, NMP_DOM_TMPC_HI) &
-                        in(lgv.tmpch2, NMP_DOM_TMPC_LO, NMP_DOM_TMPC_HI));
+      // (the 2-m pair only where it is formed and used: DIAG)
+      bool logs = in(lgv.tmpcm, NMP_DOM_TMPC_LO, NMP_DOM_TMPC_HI) &
+                  in(lgv.tmpch, NMP_DOM_TMPC_LO, NMP_DOM_TMPC_HI);
+      if constexpr (DIAG)
+        logs = logs & in(lgv.tmpcm2, NMP_DOM_TMPC_LO, NMP_DOM_TMPC_HI) &
+               in(lgv.tmpch2, NMP_DOM_TMPC_LO, NMP_DOM_TMPC_HI);
+      NMP_DOM(k, 4, logs);
       NMP_DOM(k, 5, in(zlvl - zpd, NMP_DOM_DZ_LO, NMP_DOM_DZ_HI));
       NMP_DOM(k, 6, in(hcan, NMP_DOM_HCAN_LO, NMP_DOM_HCAN_HI) &
                         in(z0m, NMP_DOM_Z0_LO, NMP_DOM_Z0_HI) &
@@ -1684,8 +1699,9 @@ DEV void sflx_column(const DevParams& P, const KArgs<T>& A, Col<T>& c, const Sin
     // saturation pressure at TGB: each iteration's closing value is the next
     // iteration's opening value (same TGB), so it is carried, not recomputed
     T es_tgb, des_tgb;
-    const Sfc1Logs<T, R> lgb = (o.sfc == 1) ? Sfc1Logs<T, R>(zlvl, zpdg, z0mg, z0h, c.status)
-                                            : Sfc1Logs<T, R>{};
+    const Sfc1Logs<T, R> lgb =
+        (o.sfc == 1) ? Sfc1Logs<T, R>(std::bool_constant<DIAG>{}, zlvl, zpdg, z0mg, z0h, c.status)
+                     : Sfc1Logs<T, R>{};
     // The bare-ground Newton loop (func.f90:3120-3200) with the division
     // policy `d`, as the canopy loop: every loop variable starts here, so a
     // lane outside the range proof's domain can run it again with IEEE
@@ -1764,10 +1780,12 @@ DEV void sflx_column(const DevParams& P, const KArgs<T>& A, Col<T>& c, const Sin
       NMP_DOM(k, 21, in(c.sfctmp, NMP_DOM_T_LO, NMP_DOM_T_HI) & in(qair, 0.0, 1.0) &
                          in(rhoair, NMP_DOM_RHO_LO, NMP_DOM_RHO_HI) &
                          in(c.sfcprs, NMP_DOM_P_LO, NMP_DOM_P_HI) & in(ur, 1.0, NMP_DOM_UR_HI));
-      NMP_DOM(k, 22, in(lgb.tmpcm, NMP_DOM_TMPC_LO, NMP_DOM_TMPC_HI) &
-                         in(lgb.tmpch, NMP_DOM_TMPC_LO, NMP_DOM_TMPC_HI) &
-                         in(lgb.tmpcm2, NMP_DOM_TMPC_LO, NMP_DOM_TMPC_HI) &
-                         in(lgb.tmpch2, NMP_DOM_TMPC_LO, NMP_DOM_TMPC_HI));
+      bool logs = in(lgb.tmpcm, NMP_DOM_TMPC_LO, NMP_DOM_TMPC_HI) &
+                  in(lgb.tmpch, NMP_DOM_TMPC_LO, NMP_DOM_TMPC_HI);
+      if constexpr (DIAG)  // as the canopy loop's
+        logs = logs & in(lgb.tmpcm2, NMP_DOM_TMPC_LO, NMP_DOM_TMPC_HI) &
+               in(lgb.tmpch2, NMP_DOM_TMPC_LO, NMP_DOM_TMPC_HI);
+      NMP_DOM(k, 22, logs);
       NMP_DOM(k, 23, in(zlvl - zpdg, NMP_DOM_DZ_LO, NMP_DOM_DZ_HI) &
                          in(z0mg, NMP_DOM_Z0_LO, NMP_DOM_Z0_HI) & in(rsurf, 0.0, NMP_DOM_RSURF_HI));
       NMP_DOM(k, 30, in(emg, 0.0, 1.0) & in(cgh, 0.0, NMP_DOM_CGH_HI));  // DTG's A
@@ -3090,9 +3108,9 @@ DEV void lds_copy_wait() {
 // phase reads them.  A macro, not a function: the kernel body inlined through
 // one more function level compiles to a different schedule, with 61 -> 101
 // spilled VGPRs (fp32 run-time math) and 31 -> 79 (fp64).
-#define NMP_LOAD_COLUMN(T, R)                                                                \
+#define NMP_LOAD_COLUMN(T, R, LEVEL)                                                         \
   Col<T> c;                                                                                  \
-  const Sink<T> out{a.diag, a.state, a.ld, a.diag_level, a.static_f, a.static_i, a.forcing,  \
+  const Sink<T> out{a.diag, a.state, a.ld, (LEVEL), a.static_f, a.static_i, a.forcing,       \
                     a.isnow, a.cost, a.ficeold, c0};                                         \
   c.tv = out.ls(NMP_S_TV); c.tg = out.ls(NMP_S_TG);                                          \
   c.fwet = out.ls(NMP_S_FWET); c.snowh = out.ls(NMP_S_SNOWH);                                \
@@ -3134,6 +3152,13 @@ DEV void lds_copy_wait() {
     }                                                                                        \
   }
 
+// OS: the compiled option set (kOptionSet), plus kNoDiag for the kernel of the
+// launches that write no diagnostics (a.diag_level == NMP_DIAG_NONE, which the
+// launch wrapper guarantees): there the output level is a constant of the
+// code, not the kernel argument (sflx_column's DIAG false).  A flag on OS, not
+// a template parameter of its own, so that every other instantiation keeps
+// its symbol name and with it its device assembly text.
+constexpr int kNoDiag = 4;
 template <class T, bool R, bool SMALL, int OS>
 __global__ __launch_bounds__(NMP_BLOCK)
 __attribute__((amdgpu_waves_per_eu(waves_per_eu<T>(SMALL))))
@@ -3173,8 +3198,9 @@ void sflx_step_kernel(const DevParams* __restrict__ gparams,
   // layer state: through the LDS copy (kPrefetch) or straight from HBM.  The
   // copy is issued first; the column's other fields load while it is in flight
   if constexpr (kPrefetch<T, R>) copy_layers_to_lds(st0, a.ld);
-  NMP_LOAD_COLUMN(T, R);
-  sflx_column<T, R, OS>(sp, a, c, out);
+  constexpr bool DIAG = !(OS & kNoDiag);
+  NMP_LOAD_COLUMN(T, R, DIAG ? a.diag_level : (int)NMP_DIAG_NONE);
+  sflx_column<T, R, OS & ~kNoDiag, DIAG>(sp, a, c, out);
   if (c.status != 0) *out.at(a.status, 0) |= c.status;
 #ifdef NMP_WAVE_TIMING
   {
@@ -3196,10 +3222,32 @@ void sflx_step_kernel(const DevParams* __restrict__ gparams,
 #endif
 }
 
-// launch wrapper of one occupancy instantiation: the kernel of option set os
+// The no-diagnostics instantiations: the fp32 `ref`-math full-occupancy
+// kernels of the compiled option sets, which spill (24 VGPRs for set 1, 37 for
+// set 2; without the diagnostics' code 13 and 32) and which five of every six
+// steps of an output-every-6th run launch.  The half-occupancy and fp64
+// kernels do not spill or write every step; the run-time-options and fast-math
+// kernels are not the production path.
+template <class T, bool R, bool SMALL>
+constexpr bool kNoDiagKernel = sizeof(T) == 4 && R && !SMALL;
+
+// launch wrapper of one occupancy instantiation: the kernel of option set os,
+// and of it the no-diagnostics one where there is one and the launch writes none
 template <class T, bool R, bool SMALL>
 void launch_os(int os, dim3 grid, dim3 block, hipStream_t stream, const DevParams* dparams,
                const KArgs<T>& a) {
+  if constexpr (kNoDiagKernel<T, R, SMALL>) {
+    if (a.diag_level == NMP_DIAG_NONE && os == 1) {
+      hipLaunchKernelGGL((sflx_step_kernel<T, R, SMALL, 1 | kNoDiag>), grid, block, 0, stream,
+                         dparams, a);
+      return;
+    }
+    if (a.diag_level == NMP_DIAG_NONE && os == 2) {
+      hipLaunchKernelGGL((sflx_step_kernel<T, R, SMALL, 2 | kNoDiag>), grid, block, 0, stream,
+                         dparams, a);
+      return;
+    }
+  }
   if (os == 1)
     hipLaunchKernelGGL((sflx_step_kernel<T, R, SMALL, 1>), grid, block, 0, stream, dparams, a);
   else if (os == 2)

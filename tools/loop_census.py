@@ -4,7 +4,8 @@
 Compiles csrc/sflx_kernel.hip to gfx950 assembly with the engine's own flags
 (build.FLAGS + build.SOURCE_FLAGS), or reads an assembly file already made, and
 prints the instruction mix of the two canopy loops of one instantiation
-(default sflx_step_kernel<float, true, false, 1>, config #3's kernel):
+(default sflx_step_kernel<float, true, false, 1>, config #3's kernel on output
+steps; --kernel IfLb1ELb0ELi5E is its no-diagnostics copy, OS 1 | kNoDiag):
 
   fast  the DivFast32 loop: short divisions and the in-range libm cores
   ref   the DivRef loop a lane outside the proven domain re-runs: IEEE

@@ -12,7 +12,8 @@ R="${GRAFT_REPO_ROOT:-/root/repo}"
 OUT="$R/gpurun_out/${TAG:-phase_ctr}"
 mkdir -p "$OUT"
 cd /tmp && export TMPDIR=/tmp
-export NOAHMP_ENGINE_LIB="$R/noahmp-1_amd/lib/variants/lib_trunc.so"
+# TRUNC_LIB: another tree's truncation library (an A/B of two builds' phases)
+export NOAHMP_ENGINE_LIB="${TRUNC_LIB:-$R/noahmp-1_amd/lib/variants/lib_trunc.so}"
 [ -f "$NOAHMP_ENGINE_LIB" ] || { echo "missing $NOAHMP_ENGINE_LIB"; exit 1; }
 P1="SQ_THREAD_CYCLES_VALU SQ_ACTIVE_INST_VALU SQ_INSTS_VALU SQ_WAVES SQ_WAVE_CYCLES SQ_BUSY_CYCLES SQ_WAIT_INST_ANY SQ_ACTIVE_INST_ANY"
 P2="SQ_INSTS_VALU_ADD_F32 SQ_INSTS_VALU_MUL_F32 SQ_INSTS_VALU_FMA_F32 SQ_INSTS_VALU_TRANS_F32 SQ_INSTS_VALU_ADD_F64 SQ_INSTS_VALU_MUL_F64 SQ_INSTS_VALU_FMA_F64 SQ_WAVES"

@@ -24,6 +24,8 @@ def demangle(name):
     if not m:
         return name
     t, r, small, os_ = m.groups()
+    # OS 5, 6: option sets 1, 2 without the diagnostics (sflx_kernel.hip kNoDiag)
+    os_ = f"{int(os_) & 3}" + (",NODIAG" if int(os_) & 4 else "")
     return f"<{'float' if t == 'f' else 'double'},R={r},SMALL={small},OS={os_}>"
 
 
@@ -46,10 +48,10 @@ def main(extra):
             rows.append(cur)
         elif cur is not None and key in KEYS:
             cur[key] = val
-    print("kernel".ljust(34) + "".join(k.split(" [")[0].rjust(13) for k in KEYS))
+    print("kernel".ljust(41) + "".join(k.split(" [")[0].rjust(13) for k in KEYS))
     for r in rows:
         if r["kernel"].startswith("<"):
-            print(r["kernel"].ljust(34) + "".join(str(r.get(k, "-")).rjust(13) for k in KEYS))
+            print(r["kernel"].ljust(41) + "".join(str(r.get(k, "-")).rjust(13) for k in KEYS))
 
 
 if __name__ == "__main__":
