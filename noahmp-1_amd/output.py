@@ -1,0 +1,197 @@
+"""The output side of the offline driver (driver.OfflineDriver):
+`OutputWriter` stages an output step's fields and writes its files on
+background threads, `Accumulation` adds the steps' fluxes up over each output
+interval on the device."""
+from __future__ import annotations
+
+import datetime
+from concurrent.futures import ThreadPoolExecutor
+
+import numpy as np
+import torch
+
+from . import layout as L, ncio
+
+
+class OutputWriter:
+    """LDASOUT (and REGIONS) files of the output steps, written while the loop
+    goes on stepping.  A single rank's output is laid on the file's grids
+    (nmp_ldasout_grid) and copied on a stream of its own and written by writer
+    threads (ncio.write_ldasout_grids).
+
+    `stage` (the rank that writes, in a run that writes output) allocates the
+    staging buffers up front: a page-locked allocation of the whole set's
+    fluxes costs tens of ms inside the time loop (the file's grids in its byte
+    order when the run has a grid; none for a regions-only run).  perm: the
+    land point of each engine column (None = grid order)."""
+    # output files in flight at once (writer threads) and staging buffers: a
+    # file's write is a memory copy into the page cache on its own thread
+    OUT_WRITERS, OUT_BUFFERS = 2, 3
+
+    def __init__(self, engine, cfg, grid, out_names, ncol_total: int, dtype, dev, stage: bool,
+                 region_plan=None, write_grids: bool = True, perm=None):
+        self.engine, self.cfg, self.grid, self.out_names = engine, cfg, grid, out_names
+        self.dev, self.region_plan, self.write_grids, self.perm = dev, region_plan, write_grids, perm
+        self.written, self.regions_written = [], []
+        nout = len(out_names)
+        self._writer = ThreadPoolExecutor(self.OUT_WRITERS)
+        self._out_host = [None] * self.OUT_BUFFERS
+        if stage and write_grids:
+            shape = (nout, ncol_total)
+            if grid is not None:
+                shape = (nout, grid.shape[0] * grid.shape[1])
+                dtype = torch.int32 if dtype == torch.float32 else torch.int64
+            self._out_host = [torch.empty(shape, dtype=dtype, pin_memory=True)
+                              for _ in range(self.OUT_BUFFERS)]
+        self._out_fut, self._n_out_w = [None] * self.OUT_BUFFERS, 0
+        # the columns' grid points and the device grids, from the first output step on
+        self._out_point, self._out_dev = None, None
+        self._reg_dev, self._reg_host = None, [None] * self.OUT_BUFFERS
+        if region_plan is not None:
+            # sums and means of an output step, and their pinned staging buffers
+            self._reg_dev = torch.zeros((2, nout, region_plan.nreg), dtype=torch.float64,
+                                        device=dev)
+            self._reg_host = [torch.empty((2, nout, region_plan.nreg), dtype=torch.float64,
+                                          pin_memory=True) for _ in range(self.OUT_BUFFERS)]
+
+    def _grids(self, d: torch.Tensor, stream) -> torch.Tensor:
+        """d laid on the file's grids in its byte order, on `stream`."""
+        if self._out_point is None:
+            idx = np.asarray(self.grid.index)
+            self._out_point = torch.as_tensor(
+                (idx if self.perm is None else idx[self.perm]).astype(np.int32), device=self.dev)
+            npts = self.grid.shape[0] * self.grid.shape[1]
+            self._out_dev = torch.empty((d.shape[0], npts), device=self.dev,
+                                        dtype=torch.int32 if d.dtype == torch.float32
+                                        else torch.int64)
+        self.engine.ldasout_grid(d, self._out_point, self._out_dev, float(ncio.FILL),
+                                 stream=stream)
+        return self._out_dev
+
+    def write(self, d: torch.Tensor, path: str, t1: datetime.datetime, stream):
+        """One output step's (16, n) fluxes (35 fields with accumulation),
+        written on a background thread:
+        on `stream` (after the step that produced them) the engine lays them
+        on the file's grids in its byte order (nmp_ldasout_grid)
+        and they are copied into the next of OUT_BUFFERS pinned host buffers;
+        a writer thread (OUT_WRITERS of them) waits for the copy and writes
+        the header and the bytes (ncio.write_ldasout_grids) while the loop
+        goes on stepping.  A buffer is reused once its previous file is
+        written.  Returns the event after which `d` has been read.
+        With regions the block is also reduced to the regions' sums and means
+        on `stream` (nmp_region_reduce), which go to a small pinned buffer of
+        the same slot; the same writer job writes the REGIONS file.  The event
+        covers the reduce.  write_grids=False leaves only that."""
+        src = None
+        if self.write_grids:
+            src = d if self.grid is None else self._grids(d, stream)
+            self.written.append(path)
+        k = self._n_out_w % self.OUT_BUFFERS
+        self._n_out_w += 1
+        if self._out_fut[k] is not None:
+            self._out_fut[k].result()
+        h, rh, rpath = self._out_host[k], None, None
+        if self.region_plan is not None:
+            rh, rpath = self._reg_host[k], ncio.regions_path(self.cfg.outdir, t1)
+            self.engine.region_reduce(d, self.region_plan, self._reg_dev[0], self._reg_dev[1],
+                                      stream=stream)
+            self.regions_written.append(rpath)
+        with torch.cuda.stream(stream):
+            if src is not None:
+                h.copy_(src, non_blocking=True)
+            if rh is not None:
+                rh.copy_(self._reg_dev, non_blocking=True)
+            ev = torch.cuda.Event()
+            ev.record(stream)
+        self._out_fut[k] = self._writer.submit(self._job, ev, None if src is None else h, path,
+                                               rh, rpath, t1)
+        return ev
+
+    def _job(self, ev, h, path, rh, rpath, t1):
+        """A writer thread's part: the files of one output step, once its copies have landed."""
+        ev.synchronize()
+        if rh is not None:
+            plan = self.region_plan
+            ncio.write_regions(rpath, plan.region_id, plan.ncolumns, plan.wsum, rh.numpy()[1], t1,
+                               self.out_names)
+        if h is None:
+            return
+        a = h.numpy()
+        if self.grid is not None:
+            ncio.write_ldasout_grids(path, self.grid, a.view(">f4" if a.itemsize == 4 else ">f8"),
+                                     t1, self.out_names)
+        else:
+            np.savez(path, time=np.array(t1.isoformat()), fields=np.array(",".join(self.out_names)),
+                     diag=a)
+
+    def flush(self):
+        """Wait until every output file issued so far is written (raises a
+        writer's error)."""
+        for f in self._out_fut:
+            if f is not None:
+                f.result()
+
+
+class Accumulation:
+    """An output interval's accumulated output (layout.BUDGET), on the device:
+    the accumulators `acc`, the scratch block `acc_diag` for the fluxes of the
+    steps between output steps (every step writes them), the water storage at
+    the interval's beginning and end, and `steps`, the steps added up so far."""
+
+    def __init__(self, engine, cs, dt: float):
+        self.engine, self.cs, self.dt = engine, cs, dt
+        n, dev, dtype = cs.ncol, cs.state.device, cs.state.dtype
+        self.acc = torch.zeros((L.NACC, n), dtype=torch.float64, device=dev)
+        self.acc_diag = torch.zeros((L.NDIAG_OUT, n), dtype=dtype, device=dev)
+        self.stor_beg = torch.zeros(n, dtype=dtype, device=dev)
+        self.stor_end = torch.zeros(n, dtype=dtype, device=dev)
+        self.start()
+
+    def start(self, acc=None, stor_beg=None, steps: int = 0):
+        """The accumulation state of an output interval: fresh (zero
+        accumulators, the beginning storage formed from the state as it is,
+        nmp_water_storage) or, part way through one, what a restart carried.
+        On the current stream, which the ranges' next step waits for."""
+        self.steps = int(steps)
+        if acc is None:
+            self.acc.zero_()
+            self.engine.water_storage(self.cs, self.stor_beg)
+            return
+        dev = self.acc.device
+        self.acc.copy_(torch.as_tensor(np.ascontiguousarray(acc, np.float64), device=dev))
+        self.stor_beg.copy_(torch.as_tensor(np.ascontiguousarray(stor_beg), device=dev))
+
+    def state(self):
+        """(acc, stor_beg, steps) of the interval so far, on the host: what a restart carries."""
+        return self.acc.cpu().numpy(), self.stor_beg.cpu().numpy(), self.steps
+
+    def restore(self, state, idx=slice(None)):
+        """`state` (state(), of the columns `idx` picks) resumes its interval;
+        None starts a fresh one from the model state as it is."""
+        if state is None:
+            self.start()
+        else:
+            self.start(state[0][:, idx], state[1][idx], state[2])
+
+    def step(self, f, diag, out: bool):
+        """One more step: (the block its fluxes go to, StreamShards.step's
+        `post`).  The output step's go into rows 0..15 of the output block
+        `diag`, the others' into the scratch block."""
+        fluxes = diag[:L.NDIAG_OUT] if out else self.acc_diag
+        self.steps += 1
+        post = self.post(fluxes, f, diag[L.NDIAG_OUT:] if out else None, self.steps * self.dt)
+        if out:
+            self.steps = 0
+        return fluxes, post
+
+    def post(self, fluxes, forcing, budget, span_s):
+        """StreamShards.step's `post` of an accumulating step: add the step's
+        fluxes and precipitation to the accumulators; at an output step
+        (budget: the output block's rows 16..34) also close the interval."""
+        def post(st, rng):
+            self.engine.accumulate(fluxes, forcing, self.acc, self.dt, stream=st, cols=rng)
+            if budget is not None:
+                self.engine.water_storage(self.cs, self.stor_end, stream=st, cols=rng)
+                self.engine.accum_finish(self.acc, self.stor_end, self.stor_beg, budget, span_s,
+                                         stream=st, cols=rng)
+        return post

@@ -128,3 +128,28 @@ class RegionPlan:
 def area_weights(lat_rad: np.ndarray) -> np.ndarray:
     """cos(latitude) in double: the relative area of a regular lat-lon cell."""
     return np.cos(np.asarray(lat_rad, np.float64))
+
+
+def plan_from_args(regions, region_weights, total: int, lat_rad=None) -> RegionPlan:
+    """The plan of the offline driver's `regions` and `region_weights`
+    arguments (driver.OfflineDriver) over the run's `total` columns.
+    lat_rad: the columns' latitudes where the caller holds all of them (a
+    single rank), what region_weights="area" weighs by; None under a process
+    group, where "area" needs the global columns' weights as an array."""
+    ids = np.asarray(regions)
+    if ids.shape != (total,):
+        raise ValueError(f"regions must hold one id per column ({total}), not {ids.shape}")
+    if isinstance(region_weights, str):
+        if region_weights == "equal":
+            w = np.ones(total, np.float64)
+        elif region_weights == "area" and lat_rad is not None:
+            w = area_weights(lat_rad)
+        elif region_weights == "area":
+            raise ValueError("region_weights='area' under a process group needs the "
+                             "global columns' weights as an array")
+        else:
+            raise ValueError("region_weights must be 'area', 'equal' or an array, not "
+                             f"{region_weights!r}")
+    else:
+        w = np.asarray(region_weights, np.float64)
+    return RegionPlan.from_ids(ids, w)

@@ -231,7 +231,8 @@ class DiagGather:
 
 
 class OutputSchedule:
-    """The output-step loop shared by bench.py and the offline driver.
+    """The output-step loop of bench.py and tests/probe_rccl_gather.py (the
+    offline driver keeps its own: calendar boundaries, not a step count).
 
     Step k writes diagnostics when (k + 1) % out_every == 0, into buffer
     (k // out_every) % nbuf, so output step j+1 fills the other buffer while

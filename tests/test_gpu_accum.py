@@ -331,14 +331,14 @@ def test_restart_mid_interval_npz(acc_run, traj, tmp_path):
     ff = lambda step, t: g["forcing"][step]  # noqa: E731
     a = driver.OfflineDriver(_cfg(tmp_path, "first"), _cols(g), forcing=ff, accumulate=True)
     a.run(nsteps=40)
-    assert a.acc_steps == 4
+    assert a.accum.steps == 4
     path = str(tmp_path / "r.npz")
     a.save_restart(path)
     a.engine.close()
     cfg = _cfg(tmp_path, "second")
     b = driver.OfflineDriver(cfg, _cols(g), forcing=ff, accumulate=True)
     b.load_restart(path)
-    assert b.step_index == 40 and b.acc_steps == 4
+    assert b.step_index == 40 and b.accum.steps == 4
     b.run()
     assert bit_equal(b.cs.state.cpu().numpy(), g["states"][-1]).all()
     b.engine.close()
@@ -357,7 +357,7 @@ def test_restart_mid_interval_npz(acc_run, traj, tmp_path):
     cfg = _cfg(tmp_path, "third")
     c = driver.OfflineDriver(cfg, _cols(g), forcing=ff, accumulate=True)
     c.load_restart(p2)
-    assert c.acc_steps == 0
+    assert c.accum.steps == 0
     c.run(nsteps=8)
     c.engine.close()
     with np.load(_npz_files(cfg.outdir)[0], allow_pickle=False) as z:
@@ -408,7 +408,7 @@ def test_restart_mid_interval_netcdf(acc_run, traj, tmp_path):
     assert got is not None and got[2] == 4
     cfg.outdir = str(tmp_path / "second")
     b = driver.OfflineDriver.from_files(cfg, init=path, accumulate=True)
-    assert b.step_index == 40 and b.acc_steps == 4
+    assert b.step_index == 40 and b.accum.steps == 4
     b.run()
     b.engine.close()
     files = _netcdf_files(cfg.outdir)

@@ -467,8 +467,65 @@ def test_driver_ingest_restart_jump_back(engine_lib, tmp_path):
     drv.save_restart(path)
     drv.run(nsteps=36)                     # on to step 60, files read ahead
     drv.load_restart(path)                 # back to step 24
-    assert drv.step_index == 24 and not drv._blocks
+    assert drv.step_index == 24 and not drv.feed.blocks
     drv.run()
     assert drv.step_index == 96
     assert bit_equal(drv.cs.state.cpu().numpy(), want).all()
+    drv.engine.close()
+
+
+@pytest.mark.parametrize("ingest", [False, True])
+def test_driver_switches_forcing_path_mid_run(engine_lib, tmp_path, ingest):
+    """Input files that differ in kind within one run: three hourly files
+    (12 steps of 900 s), the first and third standard HRLDAS files, which take
+    the resident-block path (built on the host, or ingested on the device with
+    the read-ahead), the second with CO2AIR / O2AIR of its own, whose four
+    steps take the 12-field host form.  State, ISNOW and every LDASOUT file
+    equal the same files run through the host path alone (ldasin_upload=False)
+    bit for bit, each path uploads what its files ask for, and no block older
+    than the last input time stays resident."""
+    from noahmp_amd import ncio
+    from test_config import write_case
+    from test_ncio import grid_for
+    g = load("traj_casenml.npz")
+    cols = _cols(g)
+    grid = grid_for(cols)
+    static, init, indir = tmp_path / "geo_em.d01.nc", tmp_path / "init.nc", tmp_path / "ldasin"
+    indir.mkdir()
+    nml = write_case(tmp_path)
+    text = open(nml).read().replace("'geo_em.d01.nc'", f"'{static}'").replace(
+        '"init.nc"', f'"{init}"').replace("'ldasin'", f"'{indir}'").replace(
+        "end_day = 2 end_hour = 0", "end_day = 1 end_hour = 3").replace("'3 hour'", "'1 hour'")
+    open(nml, "w").write(text)
+    cfg = config.Config(nml)
+    assert cfg.step_count() == 12
+    ncio.write_static(str(static), cols, grid)
+    ncio.write_state(str(init), grid, g["state0"], g["isnow0"], cfg.begdatetime)
+    for j, extras in enumerate((False, ("CO2AIR", "O2AIR"), False)):
+        t = cfg.begdatetime + j * cfg.input_interval
+        ncio.write_ldasin(ncio.ldasin_path(str(indir), t), grid, g["forcing"][4 * j], t,
+                          extras=extras)
+
+    def run(tag, **kw):
+        cfg.outdir = str(tmp_path / f"out_{tag}")
+        drv = driver.OfflineDriver.from_files(cfg, **kw).run()
+        assert drv.step_index == 12
+        files = sorted(glob.glob(os.path.join(cfg.outdir, "*.LDASOUT_DOMAIN1")))
+        assert len(files) == 3
+        return drv, (drv.cs.state.cpu().numpy(), drv.cs.isnow.cpu().numpy(),
+                     [open(f, "rb").read() for f in files])
+
+    ref, want = run("host", ldasin_upload=False)
+    assert ref.upload.count == 12
+    ref.engine.close()
+    drv, got = run("mixed", ingest=ingest)
+    assert bit_equal(got[0], want[0]).all() and np.array_equal(got[1], want[1])
+    assert got[2] == want[2]
+    assert drv.upload.count == 4
+    if ingest:
+        assert drv.ingest.count == 2 and drv.raw_upload.count == 0
+    else:
+        assert drv.raw_upload.count == 2 and drv.ingest is None
+    last = cfg.begdatetime + 2 * cfg.input_interval
+    assert drv.feed.blocks and not [t for t in drv.feed.blocks if t < last]
     drv.engine.close()

@@ -54,6 +54,13 @@ def write_namelist(d: str) -> str:
     return p
 
 
+# the "upload" label of a run's forcing path (feeds.feed_kind)
+UPLOAD_LABEL = {"host": "12 fields", "device-synth": "12 fields", "ldasin-step": "ldasin block",
+                "ldasin-block": "ldasin block + device cosz",
+                "ldasin-ingest": "file bytes, device ingest + cosz",
+                "ldasin-regrid": "coarse file bytes, device regrid"}
+
+
 def time_driver(cfg, precision, ldasin, warm, steps, threads, cosz="host", ingest=False, **kw):
     import torch
     t0 = time.perf_counter()
@@ -74,11 +81,8 @@ def time_driver(cfg, precision, ldasin, warm, steps, threads, cosz="host", inges
     outs = len(drv.written) - n_written
     puts = upl.count - up0
     bytes_per_put = upl.host[0].numel() * upl.host[0].element_size()
-    kind = "12 fields" if drv.raw_upload is None else (
-        "file bytes, device ingest + cosz" if drv.ingest is not None else
-        "ldasin block + device cosz" if drv.geo is not None else "ldasin block")
-    if getattr(drv, "regrid_plan", None) is not None:
-        kind = "coarse file bytes, device regrid" + (" + downscale" if drv.downscale else "")
+    kind = UPLOAD_LABEL[drv.feed.kind] + (
+        " + downscale" if drv.feed.kind == "ldasin-regrid" and drv.downscale else "")
     res = {"precision": precision, "upload": kind, "host_threads": threads, "ncol": n,
            "steps": steps, "output_steps": outs, "uploads": puts,
            "wall_s": el, "ms_per_step": el * 1e3 / steps, "colsteps_per_s": n * steps / el,
