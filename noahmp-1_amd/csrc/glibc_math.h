@@ -515,6 +515,14 @@ GM_HD float expf_inrange(float x, const GmTables& T) {
   return (float)y;
 }
 
+// expf for x < 88, -inf included: the core (which is also the full function's
+// path between its underflow bound and -88) with the underflow exit as a select.
+// Below the bound the core's value is discarded; its table index stays masked.
+GM_HD float expf_below88(float x, const GmTables& T) {
+  const float r = expf_inrange(x, T);
+  return x < -0x1.9fe368p6f ? 0.0f : r;
+}
+
 // logf for positive normal finite x, [2^-126, FLT_MAX]: x = 1 gives +0 through
 // the main path (i = 9: invc = 1, logc = 0, k = 0, r = 0), as the full
 // function's early return does
@@ -542,6 +550,35 @@ GM_HD float logf_inrange(float x, const GmTables& T) {
 // |y * log2(x)| < 126: no special-case block, no overflow / underflow exit
 GM_HD float powf_inrange(float x, float y, const GmTables& T) {
   return powf_exp2((double)y * powf_log2(asuint(x), T), 0, T);
+}
+
+// powf_tail for a positive base (sign_bias 0) with its overflow / underflow
+// exits as selects after exp2's main path: ylogx beyond either bound is beyond
+// 126 in magnitude, so the outer test of powf_tail adds nothing, and the lanes
+// that take an exit there take the same constant here.  exp2's table index is
+// masked, so a ylogx outside its range reads inside the table and its value is
+// discarded.  Equal to powf_tail(y, logx, 0, T) for every finite product
+// (tests/test_glibc_math_outloop.py).
+GM_HD float powf_tail_sel(float y, double logx, const GmTables& T) {
+  const double ylogx = (double)y * logx;
+  float r = powf_exp2(ylogx, 0, T);
+  r = ylogx > 0x1.fffffffd1d571p+6 ? __builtin_inff() : r;
+  return ylogx <= -150.0 ? 0.0f : r;
+}
+
+// log10f for positive normal finite x: fdlibm's scaling without its
+// subnormal / zero / negative / inf / NaN exits, and logf's core for the
+// mantissa in [1, 2) or [0.5, 1) (x = 1: +0 through the main path)
+GM_HD float log10f_inrange(float x, const GmTables& T) {
+  const float ivln10 = 4.3429449201e-01f;
+  const float log10_2hi = 3.0102920532e-01f, log10_2lo = 7.9034151668e-07f;
+  int32_t hx = (int32_t)asuint(x);
+  const int32_t k = (hx >> 23) - 127;
+  const int32_t i = (int32_t)(((uint32_t)k & 0x80000000u) >> 31);
+  hx = (hx & 0x007fffff) | ((0x7f - i) << 23);
+  const float y = (float)(k + i);
+  const float z = y * log10_2lo + ivln10 * logf_inrange(asfloat((uint32_t)hx), T);
+  return z + y * log10_2hi;
 }
 
 // atanf for 1 <= x < 2^25: fdlibm's three cases of that interval chosen by

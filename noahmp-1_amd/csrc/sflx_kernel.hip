@@ -60,7 +60,7 @@ DEV void twostream_all(const DevParams& P, const VegRec& V, const Opt& o, T cosz
   // leaf-angle geometry, the avmu/asu log factors, exp(-ext*vai)) or on the
   // beam (h, s1, ...) is evaluated once here, with each expression's operand
   // order unchanged, so every output is bit-identical to the 4 separate calls.
-  typedef Mth<T, R> M;
+  typedef typename GuardMth<T, R>::type M;
   const T PAI = L(3.14159265);
   T gap = L(0.0), kopen = L(0.0);
   if (vai == L(0.0)) {
@@ -198,7 +198,7 @@ struct Sfc1Logs {
   DEV Sfc1Logs() : tmpcm(0), tmpch(0), tmpcm2(0), tmpch2(0) {}
   template <class TwoM>
   DEV Sfc1Logs(TwoM, T zlvl, T zpd, T z0m, T z0h, int& status, const T* log_2z0m = nullptr) {
-    typedef Mth<T, R> M;
+    typedef typename GuardMth<T, R>::type M;
     if (zlvl <= zpd) status |= NMP_ST_ZLVL;  // :3412-3415
     tmpcm = M::log((zlvl - zpd) / z0m);
     tmpch = (z0h == z0m) ? tmpcm : M::log((zlvl - zpd) / z0h);
@@ -452,7 +452,7 @@ struct StomataPre {
 template <class T, bool R>
 DEV StomataPre<T> stomata_pre(const VegRec& V, bool any_light, T sfcprs, T sfctmp, T tv, T o2,
                               T foln, T btran, T rb) {
-  typedef Mth<T, R> M;
+  typedef typename GuardMth<T, R>::type M;
   StomataPre<T> p;
   p.cf = sfcprs / (RGAS * sfctmp) * L(1.0e06);
   p.kc = p.ko = p.awc = p.cp = p.vcmx = p.rlb = p.fnf = L(0.0);
@@ -476,7 +476,7 @@ DEV StomataPre<T> stomata_pre(const VegRec& V, bool any_light, T sfcprs, T sfctm
 template <class T, bool R, class D>
 DEV void stomata_solve(D& d, const VegRec& V, const StomataPre<T>& p, T igs, T sfcprs, T apar,
                        T ea, T ei, T co2, T& rs, T& psn) {
-  typedef Mth<T, R> M;
+  typedef typename GuardMth<T, R>::type M;
   const T CIERR = L(5.0E-2);
   const T cf = p.cf;
   rs = L(1.0) / (T)V.bp * cf;
@@ -993,7 +993,7 @@ static __device__ unsigned int nmp_wave_ctr;
 #endif
 #ifdef NMP_COUNT_FALLBACK
 static __device__ unsigned int nmp_fallback_ctr;
-static __device__ unsigned int nmp_fb_reason[64];
+// (nmp_fb_reason[64]: sflx_math.h, which counts MthGuard32's calls in 40..49)
 #endif
 
 
@@ -1013,7 +1013,7 @@ constexpr Opt kOptionSet[3] = {{1, 1, 1, 1, 1, 1, 1, 1, 2, 1, 1, 1},
 // leaves is the DIAG kernel's, bit for bit: nothing prognostic reads them.
 template <class T, bool R, int OS, bool DIAG>
 DEV void sflx_column(const DevParams& P, const KArgs<T>& A, Col<T>& c, const Sink<T>& out) {
-  typedef Mth<T, R> M;
+  typedef typename GuardMth<T, R>::type M;
 
 #ifdef NMP_PHASE_TIMING
   PhaseClock pclk{__builtin_amdgcn_s_memtime(), 0};
@@ -1162,7 +1162,7 @@ DEV void sflx_column(const DevParams& P, const KArgs<T>& A, Col<T>& c, const Sin
     const T bdsnoi = (sn_ice + sn_liq) / sn_dz;
     df_top = L(3.2217E-6) * p2(bdsnoi);
   } else {  // soil layer 1 + snow/soil interface (:1400-1444)
-    T df3 = tdfcnd<T, R>(S, c.smc[0], c.sh2o[0]);
+    T df3 = tdfcnd<T, R, M>(S, c.smc[0], c.sh2o[0]);
     if (c.lutyp == P.g.isurban) df3 = L(3.24);
     if (c.ist == 2) df3 = (c.stc[3] > TFRZ) ? TKWAT : TKICE;
     df_top = (df3 * c.dz[3] + L(0.35) * c.snowh) / (c.snowh + c.dz[3]);
@@ -1971,7 +1971,7 @@ DEV void sflx_column(const DevParams& P, const KArgs<T>& A, Col<T>& c, const Sin
     T sice = c.smc[k] - c.sh2o[k];
     c.hcpct[k + 3] = c.sh2o[k] * CWAT + (L(1.0) - smcmax) * (T)P.g.csoil +
                      (smcmax - c.smc[k]) * CPAIR + sice * CICE;
-    c.df[k + 3] = tdfcnd<T, R>(S, c.smc[k], c.sh2o[k]);
+    c.df[k + 3] = tdfcnd<T, R, M>(S, c.smc[k], c.sh2o[k]);
   }
   if (c.lutyp == P.g.isurban) {
 #pragma unroll
@@ -2105,7 +2105,7 @@ DEV void sflx_column(const DevParams& P, const KArgs<T>& A, Col<T>& c, const Sin
           supercool[k] = supercool[k] * c.dz[k] * L(1000.0);
         }
         if (o.frz == 2) {  // frh2o: func.f90:4494-4598 (sflx_routines.h)
-          const T free_ = frh2o<T, R>(smcmax, psisat, bexp, c.stc[k], c.smc[k - 3],
+          const T free_ = frh2o<T, R, M>(smcmax, psisat, bexp, c.stc[k], c.smc[k - 3],
                                       c.sh2o[k - 3], c.status);
           supercool[k] = free_ * c.dz[k] * L(1000.0);
         }
@@ -2293,7 +2293,12 @@ DEV void sflx_column(const DevParams& P, const KArgs<T>& A, Col<T>& c, const Sin
       c.fwet = rmax(L(0.0), c.canice) / rmax(maxsno, L(1.0E-06));
     else
       c.fwet = rmax(L(0.0), c.canliq) / rmax(maxliq, L(1.0E-06));
-    c.fwet = M::pow(rmin(c.fwet, L(1.0)), L(0.667));
+    // (fp32 "ref": a dry canopy's 0**0.667 is +0 for either zero, as powf gives,
+    // without taking the wave through powf's special-case block)
+    if constexpr (sizeof(T) == 4 && R)
+      c.fwet = (c.fwet == L(0.0)) ? L(0.0) : M::pow(rmin(c.fwet, L(1.0)), L(0.667));
+    else
+      c.fwet = M::pow(rmin(c.fwet, L(1.0)), L(0.667));
     if (c.canice > L(1.0E-6) && c.tv > TFRZ) {
       T qmeltc = rmin(c.canice / DT, (c.tv - TFRZ) * CICE * c.canice / DENICE / (DT * HFUS));
       c.canice = rmax(L(0.0), c.canice - qmeltc * DT);
@@ -2738,7 +2743,7 @@ DEV void sflx_column(const DevParams& P, const KArgs<T>& A, Col<T>& c, const Sin
         if (o.inf == 1) {  // wdfcnd1
           T factr = rmax(L(0.01), c.smc[k] / smcmax);
           T pw1, pw2;
-          pow_pair<T, R>(factr, expon1, expon2, pw1, pw2);
+          pow_pair<T, R, M>(factr, expon1, expon2, pw1, pw2);
           wdf[k] = dwsat * pw1;
           wdf[k] = wdf[k] * (L(1.0) - fcr[k]);
           wcnd[k] = dksat * pw2;
@@ -2747,7 +2752,7 @@ DEV void sflx_column(const DevParams& P, const KArgs<T>& A, Col<T>& c, const Sin
         } else {  // wdfcnd2
           T factr = rmax(L(0.01), c.sh2o[k] / smcmax);
           T pw1, pw2;
-          pow_pair<T, R>(factr, expon1, expon2, pw1, pw2);
+          pow_pair<T, R, M>(factr, expon1, expon2, pw1, pw2);
           wdf[k] = dwsat * pw1;
           if (sicemax > L(0.0)) {
             T vkwgt = L(1.0) / (L(1.0) + p3(L(500.0) * sicemax));

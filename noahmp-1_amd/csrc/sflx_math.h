@@ -16,7 +16,10 @@
 #include <hip/hip_runtime.h>
 #include <math.h>
 
+#include <type_traits>
+
 #include "glibc_math.h"
+#include "vege_domain.h"
 
 #define NMP_MATH_FN static __device__ __forceinline__
 
@@ -105,11 +108,15 @@ struct Mth<float, true> {
 
 // x**y1 and x**y2 with one base (wdfcnd1/wdfcnd2's WDF and WCND): each equal
 // to Mth::pow's result bit for bit.  The fp32 "ref" path forms powf's log2 of
-// x once (gm::powf_pair); the fp64 path (exp(y log x)) its log once.
-template <class T, bool R>
+// x once (gm::powf_pair, or the policy's own pow_pair: MthGuard32 below); the
+// fp64 path (exp(y log x)) its log once.
+template <class T, bool R, class M = Mth<T, R>>
 __device__ __forceinline__ void pow_pair(T x, T y1, T y2, T& r1, T& r2) {
   if constexpr (sizeof(T) == 4 && R) {
-    gm::powf_pair(x, y1, y2, gm_lds, r1, r2);
+    if constexpr (std::is_same<M, Mth<T, R>>::value)
+      gm::powf_pair(x, y1, y2, gm_lds, r1, r2);
+    else
+      M::pow_pair(x, y1, y2, r1, r2);
     return;
   }
   if constexpr (sizeof(T) == 8) {
@@ -284,6 +291,98 @@ struct MthInRange32 : Mth<float, true> {
 template <>
 struct LoopMth<float, true, DivFast32> {
   typedef MthInRange32 type;
+};
+
+// The math policy of the fp32 "ref" call sites outside the Newton loops
+// (GuardMth<T, R>::type; fp64 and "fast" math resolve to Mth<T, R>).  Those
+// arguments carry no range proof.  Each call instead tests its argument
+// against the in-range core's interval (vege_domain.h NMP_DOM_EXPF_HI, ...)
+// across the wave: one ballot and a scalar branch.  If no active lane is
+// outside, the wave runs the core, straight-line; otherwise it runs the full
+// function.  Both arms return the full function's bits on the core's interval
+// (tests/test_glibc_math_inrange.py, tests/test_glibc_math_outloop.py), so the
+// results are exact by construction, whatever the limits.  The tests are
+// written negated so that NaN counts as outside; the ballot sees active lanes
+// only, so a call under a divergent branch is not slowed by what the inactive
+// lanes' registers hold.
+//   exp:   x < 88, -inf included        -> gm::expf_below88: the core, and the
+//          underflow exit as a select.  One-sided because arguments far below
+//          -88 are everyday values here (EXP(PSI G / (RV TG)) over dry soil,
+//          EXP(-6 (ZWT - 2)) over a deep water table, EXP(-EXT VAI) at
+//          sunrise): with |x| < 88 as the test, 7.6 % of the wave-level calls
+//          took the full function (profiles/libm_outloop/fallback_rate.txt).
+//   log:   x positive, normal, finite   -> gm::logf_inrange
+//   log10: the same                     -> gm::log10f_inrange (logf's core)
+//   pow:   x positive, normal, finite and y finite, nonzero (no lane needs
+//          powf's special-case block) -> powf_log2, then powf_tail_sel: powf's
+//          own functions in powf's order, the tail's overflow / underflow
+//          exits (reachable: 0.01**26 in dry soil) as selects.
+// NMP_COUNT_FALLBACK builds count, per function, the wave-level calls and
+// those that took the full function (nmp_fb_reason 40..49).
+#ifdef NMP_COUNT_FALLBACK
+static __device__ unsigned int nmp_fb_reason[64];
+#endif
+struct MthGuard32 : Mth<float, true> {
+  // true when any active lane of the wave has `outside`; `slot`: the counters
+  static __device__ __forceinline__ bool any_outside(bool outside, int slot) {
+    const bool slow = __builtin_amdgcn_ballot_w64(outside) != 0;
+#ifdef NMP_COUNT_FALLBACK
+    const int lane = __builtin_amdgcn_mbcnt_hi(~0u, __builtin_amdgcn_mbcnt_lo(~0u, 0u));
+    if (__builtin_amdgcn_readfirstlane(lane) == lane) {  // the first active lane
+      atomicAdd(&nmp_fb_reason[slot], 1u);
+      if (slow) atomicAdd(&nmp_fb_reason[slot + 1], 1u);
+    }
+#else
+    (void)slot;
+#endif
+    return slow;
+  }
+  static __device__ __forceinline__ bool pow_base_outside(float x) {
+    return !(x >= NMP_DOM_POWF_LO && x <= NMP_DOM_POWF_HI);
+  }
+  // (the full function's arm is marked unlikely, so block placement keeps it
+  // out of the straight-line path)
+  NMP_MATH_FN float exp(float x) {
+    const bool slow = any_outside(!(x < NMP_DOM_EXPF_HI), 40);
+    if (__builtin_expect(slow, 0)) return gm::expf(x, gm_lds);
+    return gm::expf_below88(x, gm_lds);
+  }
+  NMP_MATH_FN float log(float x) {
+    const bool slow = any_outside(!(x >= NMP_DOM_LOGF_LO && x <= NMP_DOM_LOGF_HI), 42);
+    if (__builtin_expect(slow, 0)) return gm::logf(x, gm_lds);
+    return gm::logf_inrange(x, gm_lds);
+  }
+  NMP_MATH_FN float log10(float x) {
+    const bool slow = any_outside(!(x >= NMP_DOM_LOGF_LO && x <= NMP_DOM_LOGF_HI), 44);
+    if (__builtin_expect(slow, 0)) return gm::log10f(x, gm_lds);
+    return gm::log10f_inrange(x, gm_lds);
+  }
+  NMP_MATH_FN float pow(float x, float y) {
+    const bool slow =
+        any_outside(pow_base_outside(x) || gm::powf_zeroinfnan(gm::asuint(y)), 46);
+    if (__builtin_expect(slow, 0)) return gm::powf(x, y, gm_lds);
+    return gm::powf_tail_sel(y, gm::powf_log2(gm::asuint(x), gm_lds), gm_lds);
+  }
+  static __device__ __forceinline__ void pow_pair(float x, float y1, float y2, float& r1,
+                                                  float& r2) {
+    const bool slow = any_outside(pow_base_outside(x) || gm::powf_zeroinfnan(gm::asuint(y1)) ||
+                                      gm::powf_zeroinfnan(gm::asuint(y2)), 48);
+    if (__builtin_expect(slow, 0)) {
+      gm::powf_pair(x, y1, y2, gm_lds, r1, r2);
+    } else {
+      const double logx = gm::powf_log2(gm::asuint(x), gm_lds);
+      r1 = gm::powf_tail_sel(y1, logx, gm_lds);
+      r2 = gm::powf_tail_sel(y2, logx, gm_lds);
+    }
+  }
+};
+template <class T, bool R>
+struct GuardMth {
+  typedef Mth<T, R> type;
+};
+template <>
+struct GuardMth<float, true> {
+  typedef MthGuard32 type;
 };
 
 // Register-array access with a runtime index, lowered to a select chain so the

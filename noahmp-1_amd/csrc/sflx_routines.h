@@ -90,9 +90,9 @@ DEV T esat_val(T t) {
 }
 
 // tdfcnd: func.f90:1500-1595
-template <class T, bool R>
+// (M: the math policy; the step kernel passes GuardMth's)
+template <class T, bool R, class M = Mth<T, R>>
 DEV T tdfcnd(const SoilRec& S, T smc, T sh2o) {
-  typedef Mth<T, R> M;
   T smcmax = (T)S.smcmax, quartz = (T)S.quartz;
   T satratio = smc / smcmax;
   T thkw = L(0.57);
@@ -132,9 +132,8 @@ DEV T tdfcnd(const SoilRec& S, T smc, T sh2o) {
 // frh2o: func.f90:4494-4598 -- supercooled liquid water of a frozen soil
 // layer (Koren et al. 1999), Newton iteration on the log form, with the
 // Flerchinger explicit fallback (status bit) when it does not converge.
-template <class T, bool R>
+template <class T, bool R, class M = Mth<T, R>>
 DEV T frh2o(T smcmax, T psisat, T bexp, T tkelv, T smc, T sh2o, int& status) {
-  typedef Mth<T, R> M;
   T free_;
   T bx = bexp;
   if (bexp > L(5.5)) bx = L(5.5);
@@ -176,9 +175,8 @@ DEV T frh2o(T smcmax, T psisat, T bexp, T tkelv, T smc, T sh2o, int& status) {
 // its temperature derivative.  The constant sub-expressions (ELWV/RV, 1./A3,
 // A2*(A3-A4)) are folded by the reference's compiler in default real, which
 // rounds exactly as these run-time operations do.
-template <class T, bool R>
+template <class T, bool R, class M = Mth<T, R>>
 DEV void calhum(T sfctmp, T sfcprs, T& q2sat, T& dqsdt2) {
-  typedef Mth<T, R> M;
   const T A2 = L(17.67), A3 = L(273.15), A4 = L(29.65), ELWV = L(2.501E6);
   const T A23M4 = A2 * (A3 - A4), E0 = L(0.611), RV = L(461.0), EPS = L(0.622);
   const T es = E0 * M::exp(ELWV / RV * (L(1.) / A3 - L(1.) / sfctmp));

@@ -168,6 +168,29 @@
 #define NMP_DOM_MOZG_LO -1.0e16
 #endif
 
+// ---- the libm calls outside the Newton loops (sflx_math.h MthGuard32).  No
+// range proof: each call tests its argument against the core's documented
+// interval across the wave and runs the full function when any active lane is
+// outside, so the limits below change the speed and never a result.  They are
+// the cores' own intervals (glibc_math.h): expf for x < 88; logf, log10f and
+// powf's base over the positive normal floats.  A probe build narrows them
+// (tests/probe_libm_outloop.py) to send most waves through the full functions.
+#ifndef NMP_DOM_EXPF_HI
+#define NMP_DOM_EXPF_HI 88.0f
+#endif
+#ifndef NMP_DOM_LOGF_LO
+#define NMP_DOM_LOGF_LO 0x1p-126f
+#endif
+#ifndef NMP_DOM_LOGF_HI
+#define NMP_DOM_LOGF_HI 0x1.fffffep+127f
+#endif
+#ifndef NMP_DOM_POWF_LO
+#define NMP_DOM_POWF_LO 0x1p-126f
+#endif
+#ifndef NMP_DOM_POWF_HI
+#define NMP_DOM_POWF_HI 0x1.fffffep+127f
+#endif
+
 // ---- the stomata bisection (stomata, func.f90:3739-3887; sflx_kernel.hip
 // stomata_solve), run in the canopy loop's first iteration.  Its six divisions
 // per bisection step use DivFast32 when, besides the canopy loop's domain

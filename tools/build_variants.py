@@ -19,6 +19,10 @@ VARIANTS = {
     # the default build plus a device counter of lanes that re-ran the canopy
     # loop with IEEE division (nmp_debug_fallback_count)
     "fbcount": {"f32": ["-DNMP_COUNT_FALLBACK"]},
+    # the libm calls outside the Newton loops (sflx_math.h MthGuard32) with their
+    # intervals narrowed: most waves run the full functions (tests/probe_libm_outloop.py)
+    "probe_libm_outloop": {"f32": ["-DNMP_COUNT_FALLBACK", "-DNMP_DOM_EXPF_HI=-1.0e30f",
+                                   "-DNMP_DOM_LOGF_LO=1.0e30f", "-DNMP_DOM_POWF_LO=1.0e30f"]},
     "gmbl": ("-DNMP_GM_BRANCHLESS=1",),
     "b128": ("-DNMP_BLOCK=128",),
     "b64": ("-DNMP_BLOCK=64",),
