@@ -24,6 +24,14 @@ typedef ORACLE_REAL real;
 #define ORACLE_IS_FLOAT (sizeof(real) == 4)
 #define K(x) ((real)(ORACLE_IS_FLOAT ? (double)(x##f) : (x)))
 
+/* The composite 2-m temperature T2M (func.f90:1256/1270), which is not one of
+ * the 58 outputs: oracle_set_t2m(buf) makes every following batch store it per
+ * column into buf (NULL: off).  The arithmetic and the output layout are
+ * unchanged. */
+static real* g_t2m;
+static int32_t g_col;
+void oracle_set_t2m(real* buf) { g_t2m = buf; }
+
 /* Loop trip counts per column (tools/iter_stats.py; build with -DORACLE_ITER_STATS
  * only): 0 vege_flux Newton, 1 stomata bisection, 2 frh2o, 3 soilwater
  * sub-steps, 4 bare_flux Newton. */
@@ -60,7 +68,107 @@ void oracle_set_branches(uint32_t* buf) { g_br = buf; }
  * site the smallest / largest |a|, |b|, |a/b| over nonzero finite values and
  * the count of zero numerators.  The arithmetic is unchanged: DV(k, a, b) is
  * a / b. */
-#ifdef ORACLE_DIV_STATS
+#if defined(ORACLE_PERTURB)
+/* Perturbed fp64 build (-DORACLE_DOUBLE -DORACLE_ITER_STATS -DORACLE_PERTURB;
+ * port.step_ensemble, tests/test_fp64_envelope.py): every value the fp64 engine
+ * forms differently from this restatement is scaled by (1 + s b A 2^-52), with
+ *   b  the site's bound in ulps (an ulp taken as 2^-52 of the value, its
+ *      largest relative size), set from Python (oracle_set_perturb_bounds: the
+ *      recorded device maxima of profiles/math64/ulp.json plus the margin
+ *      tests/test_gpu_math64.py asserts them with),
+ *   A  the amplitude (1 for the ensemble; larger to show the recorder is live),
+ *   s  in {-1, 0, +1} by the member's mode: 0 off (bit-identical to the plain
+ *      build), 1 all +, 2 all -, 3 / 4 the sign alternating by site kind,
+ *      5 a hash of (seed, column in the batch, running call count in the column).
+ * Zero, infinite and NaN values pass through unchanged; SQRT, FABS, FMOD,
+ * COPYSIGN and every plain operation stay exact.
+ *
+ * Sites (the places where csrc/ evaluates an expression differently in fp64):
+ *   the libm calls        exp exp2 log log10 tanh atan tan acos cos: ocml on
+ *                         the device, glibc here; b = E_fn.
+ *   POW(x, y)             Mth<double>::pow = exp(y log x):
+ *                         b = 2 (E_log + 0.5) |y ln x| + E_exp (sflx_math.h).
+ *                         pow_pair<double> is two such calls bit for bit.
+ *   POW(x, +-0.25)        pow_q = sqrt(sqrt(x)), pow_mq = 1 / pow_q: 1.5 and
+ *                         2.5 ulp from the correctly rounded power (sflx_math.h),
+ *                         plus the margin: b = PB_POWQ, PB_POWMQ.  Every
+ *                         POW(., +-0.25) here is a pow_q / pow_mq call there
+ *                         (sfcdif1, ragrb, TRAD).
+ *   DV(k, a, b), DVN(a, b) the divisions of the Newton loops (vege_flux with
+ *                         stomata, sfcdif1 and ragrb, the under-canopy loop,
+ *                         bare_flux, EVC's limit), which the fp64 kernel forms
+ *                         as dv<double>: a refined reciprocal times the
+ *                         numerator, within 1 ulp of the IEEE quotient
+ *                         (sflx_math.h): b = PB_DIV = 1.  Every other division
+ *                         of the kernel is IEEE `/`, as here.
+ *   tdfcnd's THKSAT       TKICE**(SMCMAX-XU) * THKW**XU as one exp of
+ *                         t = (SMCMAX-XU) ln TKICE + XU ln THKW with the type-only
+ *                         factor THKS**(1-SMCMAX) from the host's libm (which is
+ *                         this file's): see tdfcnd.
+ *   zwt's SMPFZ           a double pow in every precision: ocml's pow on the
+ *                         device, b = PB_POWD (ocml's stated 1 ulp + margin).
+ * The `(sizeof(T) == 4 && R) ? table : expr` sites of the kernel evaluate this
+ * file's own expression in fp64 and need no site. */
+enum { PB_EXP, PB_EXP2, PB_LOG, PB_LOG10, PB_TANH, PB_ATAN, PB_TAN, PB_ACOS, PB_COS,
+       PB_POW, PB_POWQ, PB_POWMQ, PB_DIV, PB_TDF, PB_POWD, PB_N };
+static double g_pb[PB_N];
+static int g_pmode;
+static uint64_t g_pseed;
+static double g_pamp = 1.0;
+static int32_t g_pcol;
+static uint32_t g_pcall;
+void oracle_set_perturb(uint64_t seed, int mode, double amplitude) {
+  g_pseed = seed;
+  g_pmode = mode;
+  g_pamp = amplitude;
+}
+/* b[PB_EXP .. PB_COS], b[PB_POWQ], b[PB_POWMQ], b[PB_DIV], b[PB_POWD] in ulps;
+ * PB_POW and PB_TDF are formed per call from PB_LOG and PB_EXP */
+void oracle_set_perturb_bounds(const double* b, int n) {
+  for (int k = 0; k < PB_N; ++k) g_pb[k] = k < n ? b[k] : 0.0;
+}
+static inline double pert(int site, double r, double bound) {
+  if (g_pmode == 0) return r;
+  const uint32_t call = g_pcall++;
+  if (r == 0.0 || !isfinite(r)) return r;
+  double s;
+  switch (g_pmode) {
+    case 1: s = 1.0; break;
+    case 2: s = -1.0; break;
+    case 3: s = (site & 1) ? -1.0 : 1.0; break;
+    case 4: s = (site & 1) ? 1.0 : -1.0; break;
+    default: {  /* splitmix64 of (seed, column, call) */
+      uint64_t z = g_pseed * 0x9E3779B97F4A7C15ull + ((uint64_t)(uint32_t)g_pcol << 32 | call);
+      z = (z ^ (z >> 30)) * 0xBF58476D1CE4E5B9ull;
+      z = (z ^ (z >> 27)) * 0x94D049BB133111EBull;
+      z ^= z >> 31;
+      s = (double)(int)(z % 3) - 1.0;
+    }
+  }
+  return r * (1.0 + s * bound * g_pamp * 0x1p-52);
+}
+static inline double p_exp(double x) { return pert(PB_EXP, exp(x), g_pb[PB_EXP]); }
+static inline double p_exp2(double x) { return pert(PB_EXP2, exp2(x), g_pb[PB_EXP2]); }
+static inline double p_log(double x) { return pert(PB_LOG, log(x), g_pb[PB_LOG]); }
+static inline double p_log10(double x) { return pert(PB_LOG10, log10(x), g_pb[PB_LOG10]); }
+static inline double p_tanh(double x) { return pert(PB_TANH, tanh(x), g_pb[PB_TANH]); }
+static inline double p_atan(double x) { return pert(PB_ATAN, atan(x), g_pb[PB_ATAN]); }
+static inline double p_tan(double x) { return pert(PB_TAN, tan(x), g_pb[PB_TAN]); }
+static inline double p_acos(double x) { return pert(PB_ACOS, acos(x), g_pb[PB_ACOS]); }
+static inline double p_cos(double x) { return pert(PB_COS, cos(x), g_pb[PB_COS]); }
+static inline double p_pow(double x, double y) {
+  const double r = pow(x, y);
+  if (g_pmode == 0) return r;
+  if (y == 0.25) return pert(PB_POWQ, r, g_pb[PB_POWQ]);
+  if (y == -0.25) return pert(PB_POWMQ, r, g_pb[PB_POWMQ]);
+  const double t = fabs(y * log(x));  /* infinite or NaN only where r passes through */
+  return pert(PB_POW, r, 2.0 * (g_pb[PB_LOG] + 0.5) * (isfinite(t) ? t : 0.0) + g_pb[PB_EXP]);
+}
+static inline double p_div(double a, double b) { return pert(PB_DIV, a / b, g_pb[PB_DIV]); }
+#define DV(k, a, b) p_div((a), (b))
+#define DVN(a, b) p_div((a), (b))
+#define PERT_SITE(site, r, bound) pert((site), (r), (bound))
+#elif defined(ORACLE_DIV_STATS)
 #define NDIVSITE 40
 static double g_div[NDIVSITE][8];
 static int g_div_init;
@@ -95,8 +203,29 @@ static inline real div_stat(int k, real a, real b) {
 #else
 #define DV(k, a, b) ((a) / (b))
 #endif
+/* the Newton-loop divisions outside the canopy loop's numbered sites, and the
+ * other values only the perturbed build touches: plain in every other build */
+#ifndef ORACLE_PERTURB
+#define DVN(a, b) ((a) / (b))
+#define PERT_SITE(site, r, bound) (r)
+#endif
 
-#if defined(ORACLE_DOUBLE)
+#if defined(ORACLE_PERTURB)
+#define EXP p_exp
+#define LOG p_log
+#define LOG10 p_log10
+#define POW p_pow
+#define SQRT sqrt
+#define TANH p_tanh
+#define ATAN p_atan
+#define TAN p_tan
+#define ACOS p_acos
+#define COS p_cos
+#define FABS fabs
+#define FMOD fmod
+#define EXP2 p_exp2
+#define COPYSIGN copysign
+#elif defined(ORACLE_DOUBLE)
 #define EXP exp
 #define LOG log
 #define LOG10 log10
@@ -302,10 +431,30 @@ static real tdfcnd(const nmp_params* P, int sltyp, real SMC, real soilwat) {
   real THKW = K(0.57);
   real THKQTZ = K(7.7);
   /* THKO = 2.0: pow(2.0, x) is lowered to exp2 by the reference's compiler */
+#ifdef ORACLE_PERTURB
+  /* The fp64 kernel takes THKS**(1-SMCMAX) from the host (dev_params.h: this
+   * expression through the host's libm, exact here) and forms the rest as
+   * exp(t), t = a c1 + XU c2 with a = SMCMAX-XU, c1 = ln TKICE, c2 = ln THKW
+   * rounded to double.  Each constant and each product carries 2^-53 relative,
+   * the sum 2^-53 of |t| <= |a c1| + |XU c2|: t is off by at most
+   * 3 (|a c1| + |XU c2|) 2^-53, which exp turns into that relative error of
+   * its result, <= 3 (|a c1| + |XU c2|) ulp; exp adds E_exp and the product
+   * with the host factor 0.5.  This side's own two pow results and two
+   * products add 2 more: b = E_exp + 3 (|a c1| + |XU c2|) + 2.5. */
+  real THKS = pow(THKQTZ, SOILP(quartz)) * exp2(K(1.0) - SOILP(quartz));
+  real XUNFROZ = soilwat / SMC;
+  real XU = XUNFROZ * SOILP(smcmax);
+  real THKSAT = pow(THKS, K(1.0) - SOILP(smcmax)) * pow(TKICE, SOILP(smcmax) - XU) * pow(THKW, XU);
+  {
+    const double tb = fabs((SOILP(smcmax) - XU) * 0.7884573603642703) + fabs(XU * 0.5621189181535413);
+    THKSAT = PERT_SITE(PB_TDF, THKSAT, g_pb[PB_EXP] + 3.0 * (isfinite(tb) ? tb : 0.0) + 2.5);
+  }
+#else
   real THKS = POW(THKQTZ, SOILP(quartz)) * EXP2(K(1.0) - SOILP(quartz));
   real XUNFROZ = soilwat / SMC;
   real XU = XUNFROZ * SOILP(smcmax);
   real THKSAT = POW(THKS, K(1.0) - SOILP(smcmax)) * POW(TKICE, SOILP(smcmax) - XU) * POW(THKW, XU);
+#endif
   real GAMMD = (K(1.0) - SOILP(smcmax)) * K(2700.0);
   real THKDRY = (K(0.135) * GAMMD + K(64.7)) / (K(2700.0) - K(0.947) * GAMMD);
   real AKE;
@@ -872,19 +1021,19 @@ static void stomata(const nmp_params* P, int lutyp, real igs, real sfcprs, real 
      * initialised); for C3C4 outside {1,2} we use that initial NaN. */
     real wc = NAN, wj = NAN, we = NAN;
     if (c3c4 == 1) {
-      wj = rmax(ci - cp, K(0.0)) * j / (ci + K(2.0) * cp);
-      wc = rmax(ci - cp, K(0.0)) * vcmx / (ci + awc);
+      wj = DVN(rmax(ci - cp, K(0.0)) * j, (ci + K(2.0) * cp));
+      wc = DVN(rmax(ci - cp, K(0.0)) * vcmx, (ci + awc));
       we = K(0.5) * vcmx;
     } else if (c3c4 == 2) {
       BR(3);
       wj = j;
       wc = vcmx;
-      we = K(4000.0) * vcmx * ci / sfcprs;
+      we = DVN(K(4000.0) * vcmx * ci, sfcprs);
     }
     *psn = rmin(rmin(wj, wc), we) * igs;
     real cs = rmax(co2 - K(1.37) * rlb * sfcprs * *psn, MPE);
-    real a = VEGP(mp) * *psn * sfcprs * ea / (cs * ei) + VEGP(bp);
-    real b = (VEGP(mp) * *psn * sfcprs / cs + VEGP(bp)) * rlb - K(1.0);
+    real a = DVN(VEGP(mp) * *psn * sfcprs * ea, (cs * ei)) + VEGP(bp);
+    real b = (DVN(VEGP(mp) * *psn * sfcprs, cs) + VEGP(bp)) * rlb - K(1.0);
     real c = -rlb;
     real q;
     if (b >= K(0.0)) {
@@ -894,8 +1043,8 @@ static void stomata(const nmp_params* P, int lutyp, real igs, real sfcprs, real 
       q = K(-0.5) * (b - SQRT(b * b - K(4.0) * a * c));
       b_nonneg = 0;
     }
-    real r1 = q / a;
-    real r2 = c / q;
+    real r1 = DVN(q, a);
+    real r2 = DVN(c, q);
     *rs = rmax(r1, r2);
     real fci = rmax(cs - *psn * sfcprs * K(1.65) * *rs, K(0.0));
     if (((cihigh - cilow) <= CIERR) || FABS(fci - ci) <= MPE) break;
@@ -1046,9 +1195,9 @@ static void vege_flux(ctx_t* X, int ISNOW, int lutyp, real DT, real SAV, real SA
     o->EVC = DV(34, fveg * RHOAIR * CPAIR * CEW * (ESTV - *EAH), GAMMAV);
     o->TR = DV(35, fveg * RHOAIR * CPAIR * CTW * (ESTV - *EAH), GAMMAV);
     if (*TV > TFRZ)
-      o->EVC = rmin(CANLIQ * LATHEAV / DT, o->EVC);
+      o->EVC = rmin(DVN(CANLIQ * LATHEAV, DT), o->EVC);
     else
-      o->EVC = rmin(CANICE * LATHEAV / DT, o->EVC);
+      o->EVC = rmin(DVN(CANICE * LATHEAV, DT), o->EVC);
     B = SAV - o->IRC - o->SHC - o->EVC - o->TR;
     A = fveg * (K(4.0) * CIR * p3(*TV) + CSH + (CEV + CTR) * DESTV);
     DTV = DV(36, B, A);
@@ -1086,7 +1235,7 @@ static void vege_flux(ctx_t* X, int ISNOW, int lutyp, real DT, real SAV, real SA
     o->GH = CGH * (*TG - STC[ISNOW + 1]);
     B = SAG - o->IRG - o->SHG - o->EVG - o->GH;
     A = K(4.0) * CIR * p3(*TG) + CSH + CEV * DESTG + CGH;
-    DTG = B / A;
+    DTG = DVN(B, A);
     o->IRG = o->IRG + K(4.0) * CIR * p3(*TG) * DTG;
     o->SHG = o->SHG + CSH * DTG;
     o->EVG = o->EVG + CEV * DESTG * DTG;
@@ -1158,9 +1307,9 @@ static void bare_flux(ctx_t* X, int lutyp, int ISNOW, real SAG, real LWDN, real 
       }
     }
     RAMB = rmax(K(1.0), K(1.0) / (*CM * UR));
-    RAHB = rmax(K(1.0), K(1.0) / (*CH * UR));
+    RAHB = rmax(K(1.0), DVN(K(1.0), (*CH * UR)));
     RAWB = RAHB;
-    EHB = K(1.0) / RAHB;
+    EHB = DVN(K(1.0), RAHB);
     T = tdc(*TGB);
     esat(T, &ESATW, &ESATI, &DSATW, &DSATI);
     if (T > K(0.0)) {
@@ -1170,15 +1319,15 @@ static void bare_flux(ctx_t* X, int lutyp, int ISNOW, real SAG, real LWDN, real 
       ESTG = ESATI;
       DESTG = DSATI;
     }
-    CSH = RHOAIR * CPAIR / RAHB;
-    CEV = RHOAIR * CPAIR / GAMMA / (RSURF + RAWB);
+    CSH = DVN(RHOAIR * CPAIR, RAHB);
+    CEV = DVN(DVN(RHOAIR * CPAIR, GAMMA), (RSURF + RAWB));
     o->IRB = CIR * p4(*TGB) - EMG * LWDN;
     o->SHB = CSH * (*TGB - SFCTMP);
     o->EVB = CEV * (ESTG * RHSUR - EAIR);
     o->GHB = CGH * (*TGB - STC[ISNOW + 1]);
     B = SAG - o->IRB - o->SHB - o->EVB - o->GHB;
     A = K(4.0) * CIR * p3(*TGB) + CSH + CEV * DESTG + CGH;
-    DTG = B / A;
+    DTG = DVN(B, A);
     o->IRB = o->IRB + K(4.0) * CIR * p3(*TGB) * DTG;
     o->SHB = o->SHB + CSH * DTG;
     o->EVB = o->EVB + CEV * DESTG * DTG;
@@ -2281,7 +2430,8 @@ static void groundwater(const nmp_params* P, int sltyp, real DT, const real* ZSO
   *QDIS = (K(1.0) - FCRMAX) * RSBMX * EXP(-(real)P->timean) * EXP(-FFF * (*ZWT - K(2.0)));
   double S_NODE = (double)rmin(K(1.0), SMC[IWT] / SOILP(smcmax));
   S_NODE = fmax(S_NODE, (double)0.01f);
-  real SMPFZ = (real)(-((double)(SOILP(psisat) * K(1000.0)) * pow(S_NODE, (double)(-SOILP(bexp)))));
+  real SMPFZ = (real)(-((double)(SOILP(psisat) * K(1000.0)) *
+                        PERT_SITE(PB_POWD, pow(S_NODE, (double)(-SOILP(bexp))), g_pb[PB_POWD])));
   SMPFZ = rmax(K(-120000.0), CMIC * SMPFZ);
   real KA = HK[IWT];
   real WH_ZWT = -*ZWT * K(1.0E3);
@@ -2831,7 +2981,7 @@ static void sflx_column(ctx_t* X, real DT, int YEARLEN, real JULIAN, const real 
   d[NMP_D_IRC] = IRC; d[NMP_D_IRB] = bo.IRB; d[NMP_D_TR] = TR; d[NMP_D_EVC] = EVC;
   d[NMP_D_CHLEAF] = CHLEAF; d[NMP_D_CHUC] = CHUC; d[NMP_D_CHV2] = CHV2; d[NMP_D_CHB2] = bo.EHB2;
   d[NMP_D_FPICE] = wo.FPICE;
-  (void)T2M;
+  if (g_t2m) g_t2m[g_col] = T2M;
 }
 
 int oracle_real_bytes(void) { return (int)sizeof(real); }
@@ -2840,8 +2990,13 @@ int oracle_sflx_batch(int32_t n, real dt, int32_t yearlen, real julian, const re
                       real* st, int32_t* isnow, const real* sf, const int32_t* si, const real* fc,
                       real* dg, int32_t* status, const nmp_params* P, const nmp_options* O) {
   for (int32_t c = 0; c < n; ++c) {
+    g_col = c;
 #ifdef ORACLE_ITER_STATS
     g_stat_col = c;
+#endif
+#ifdef ORACLE_PERTURB
+    g_pcol = c; /* a member is a function of (seed, column, call): reproducible */
+    g_pcall = 0;
 #endif
 #ifdef ORACLE_BRANCH_STATS
     g_br_col = c;

@@ -3,6 +3,12 @@
 ctypes driver for the plain-C restatement (oracle/noahmp_oracle.c), built as
 build/liboracle_f32.so and build/liboracle_f64.so by oracle/Makefile.
 Same SoA interface as oracle/ref.py.
+
+step_ensemble / run_ensemble drive the perturbed fp64 build
+(build/liboracle_f64_perturb.so, noahmp_oracle.c ORACLE_PERTURB): the base and
+members whose libm results, powers and Newton-loop divisions are moved within
+bounds the caller passes.  The fp64 engine's GPU tests take their per-column
+tolerance from it (tests/golden_io.py check_fp64_rule).
 """
 from __future__ import annotations
 
@@ -21,7 +27,17 @@ LIBS = {4: os.path.join(HERE, "build", "liboracle_f32.so"),
         "8s": os.path.join(HERE, "build", "liboracle_f64_stats.so"),
         "4d": os.path.join(HERE, "build", "liboracle_f32_divstats.so"),
         "4b": os.path.join(HERE, "build", "liboracle_f32_brstats.so"),
-        "8b": os.path.join(HERE, "build", "liboracle_f64_brstats.so")}
+        "8b": os.path.join(HERE, "build", "liboracle_f64_brstats.so"),
+        "8p": os.path.join(HERE, "build", "liboracle_f64_perturb.so")}
+_F64 = (8, "8s", "8b", "8p")
+# the perturbed fp64 build's site kinds, in the order of noahmp_oracle.c's PB_
+# enum ("pow" and "tdf" are formed per call from "log" and "exp"): the keys of
+# the bounds dict step_ensemble takes, in ulps
+PERTURB_SITES = ("exp", "exp2", "log", "log10", "tanh", "atan", "tan", "acos", "cos",
+                 "pow", "pow_q", "pow_mq", "div", "tdf", "pow_d")
+# ensemble members as (mode, seed): the four fixed sign patterns and 24 seeds
+FIXED_MEMBERS = ((1, 0), (2, 0), (3, 0), (4, 0))
+ENSEMBLE = FIXED_MEMBERS + tuple((5, s) for s in range(1, 25))
 # trip counts recorded by the stats builds, per column (noahmp_oracle.c ITER_STAT)
 STAT_LOOPS = ("vege_flux Newton", "stomata bisection", "frh2o", "soilwater sub-steps",
               "bare_flux Newton")
@@ -65,17 +81,22 @@ def _lib(precision):
         if not available(precision):
             raise FileNotFoundError(f"{LIBS[precision]} missing (run make -C oracle port)")
         lib = C.CDLL(LIBS[precision])
-        rt = np.float64 if precision in (8, "8s", "8b") else np.float32
+        rt = np.float64 if precision in _F64 else np.float32
         rp = np.ctypeslib.ndpointer(rt, flags="C_CONTIGUOUS")
         ip = np.ctypeslib.ndpointer(np.int32, flags="C_CONTIGUOUS")
-        creal = C.c_double if precision in (8, "8s", "8b") else C.c_float
+        creal = C.c_double if precision in _F64 else C.c_float
         lib.oracle_sflx_batch.argtypes = [C.c_int32, creal, C.c_int32, creal, rp, rp, ip, rp, ip,
                                           rp, rp, ip, C.c_char_p, C.c_void_p]
         lib.oracle_sflx_run.argtypes = [C.c_int32, C.c_int32, creal, C.c_int32, creal, rp, rp, ip,
                                         rp, ip, rp, C.c_int32, rp, ip, C.c_char_p, C.c_void_p]
-        assert lib.oracle_real_bytes() == (8 if precision in (8, "8s", "8b") else 4)
-        if precision in ("4s", "8s"):
+        assert lib.oracle_real_bytes() == (8 if precision in _F64 else 4)
+        if precision in ("4s", "8s", "8p"):
             lib.oracle_set_stats.argtypes = [C.c_void_p]
+        if precision == "8p":
+            lib.oracle_set_perturb.argtypes = [C.c_uint64, C.c_int, C.c_double]
+            lib.oracle_set_perturb_bounds.argtypes = [
+                np.ctypeslib.ndpointer(np.float64, flags="C_CONTIGUOUS"), C.c_int]
+        lib.oracle_set_t2m.argtypes = [C.c_void_p]
         if precision == "4d":
             lib.oracle_div_stats.argtypes = [C.c_void_p, C.c_int]
         if precision in ("4b", "8b"):
@@ -105,6 +126,21 @@ def step(P: dict, options, zsoil, dt, yearlen, julian, state, isnow, static_f, s
     return st.T.copy(), isn, dg.T.copy(), status
 
 
+def step_t2m(P: dict, options, zsoil, dt, yearlen, julian, state, isnow, static_f, static_i,
+             forcing, precision=4):
+    """step() plus the composite 2-m temperature T2M (func.f90:1256/1270), which
+    is not one of the 58 outputs, as an (n,) array (oracle_set_t2m)."""
+    lib, rt = _lib(precision)
+    t2m = np.zeros(isnow.shape[0], rt)
+    lib.oracle_set_t2m(t2m.ctypes.data)
+    try:
+        out = step(P, options, zsoil, dt, yearlen, julian, state, isnow, static_f, static_i,
+                   forcing, precision=precision)
+    finally:
+        lib.oracle_set_t2m(None)
+    return (*out, t2m)
+
+
 def step_stats(P: dict, options, zsoil, dt, yearlen, julian, state, isnow, static_f, static_i,
                forcing, precision=4):
     """step() through the trip-count build of `precision` (4 or 8): returns
@@ -120,6 +156,81 @@ def step_stats(P: dict, options, zsoil, dt, yearlen, julian, state, isnow, stati
     finally:
         lib.oracle_set_stats(None)
     return (*out, buf[:, :len(STAT_LOOPS)].copy())
+
+
+def _member_step(bounds, mode, seed, amplitude, args):
+    """One step of the perturbed fp64 build as member (mode, seed): step()'s
+    tuple, the (n, 5) trip counts and T2M."""
+    lib, _ = _lib("8p")
+    b = np.array([float(bounds.get(k, 0.0)) for k in PERTURB_SITES], np.float64)
+    lib.oracle_set_perturb_bounds(b, b.size)
+    n = args[7].shape[0]
+    buf = np.zeros((n, 8), np.int32)
+    t2m = np.zeros(n, np.float64)
+    lib.oracle_set_perturb(int(seed), int(mode), float(amplitude))
+    lib.oracle_set_stats(buf.ctypes.data)
+    lib.oracle_set_t2m(t2m.ctypes.data)
+    try:
+        out = step(*args, precision="8p")
+    finally:
+        lib.oracle_set_stats(None)
+        lib.oracle_set_t2m(None)
+        lib.oracle_set_perturb(0, 0, 1.0)
+    return (*out, buf[:, :len(STAT_LOOPS)].copy(), t2m)
+
+
+def _deviation(member, base):
+    """Per column, the largest |member - base| / (1e-9 (1 + |base|)) over the
+    fields of an (nfield, n) array; fields equal in bits (NaN == NaN, inf ==
+    inf) count 0, a finite value against a non-finite one inf."""
+    member, base = np.asarray(member, np.float64), np.asarray(base, np.float64)
+    same = (member == base) | (np.isnan(member) & np.isnan(base))
+    with np.errstate(invalid="ignore", over="ignore"):
+        q = np.abs(member - base) / (1e-9 * (1.0 + np.abs(base)))
+    q = np.where(same, 0.0, np.where(np.isnan(q), np.inf, q))
+    return q.max(axis=0) if q.ndim > 1 else q
+
+
+def step_ensemble(P: dict, options, zsoil, dt, yearlen, julian, state, isnow, static_f, static_i,
+                  forcing, bounds, members=ENSEMBLE, amplitude=1.0):
+    """The fp64 restatement (mode 0 of the perturbed build) and an ensemble of
+    its perturbed members over one step.
+
+    bounds: {site kind: ulps} for PERTURB_SITES (missing kinds: 0).  Returns
+    (base, discrete, q): base = (state', isnow', diag(58, n), status, trips(n, 5),
+    T2M(n)); discrete(n,) = a member changed ISNOW, status or a trip count;
+    q(n,) = the largest member deviation over the state, the 58 outputs and
+    T2M, in units of 1e-9 (1 + |base|)."""
+    return run_ensemble(P, options, zsoil, dt, yearlen, [julian], state, isnow, static_f,
+                        static_i, [forcing], bounds, members, amplitude)
+
+
+def run_ensemble(P: dict, options, zsoil, dt, yearlen, julians, state, isnow, static_f, static_i,
+                 forcings, bounds, members=ENSEMBLE, amplitude=1.0):
+    """step_ensemble over repeated steps (julians[k], forcings[k]): each member
+    is perturbed in every step; the trip counts of all steps are compared, the
+    values after the last; status is the OR over the steps.  The base carries the
+    last step's outputs."""
+    def go(mode, seed):
+        st, isn, trips, status = state, isnow, [], 0
+        for k, (jul, f) in enumerate(zip(julians, forcings)):
+            st, isn, dg, stat_k, it, t2m = _member_step(
+                bounds, mode, 1000003 * k + seed, amplitude,
+                (P, options, zsoil, dt, yearlen, jul, st, isn, static_f, static_i, f))
+            trips.append(it)
+            status = status | stat_k   # sticky over the steps, like the engine's status word
+        return st, isn, dg, status, np.concatenate(trips, axis=1), t2m
+    base = go(0, 0)
+    n = base[1].shape[0]
+    discrete = np.zeros(n, bool)
+    q = np.zeros(n)
+    for mode, seed in members:
+        m = go(mode, seed)
+        discrete |= (m[1] != base[1]) | (m[3] != base[3]) | (m[4] != base[4]).any(axis=1)
+        q = np.maximum(q, np.maximum(np.maximum(_deviation(m[0], base[0]),
+                                                _deviation(m[2], base[2])),
+                                     _deviation(m[5], base[5])))
+    return base, discrete, q
 
 
 def step_branches(P: dict, options, zsoil, dt, yearlen, julian, state, isnow, static_f, static_i,

@@ -180,3 +180,128 @@ def check_fp64_trajectory_step(name, s, st, isn, dg, g, k):
             assert ok[0], (name, s, "the run/case.nml column is outside the x10 trajectory bar")
         assert ok.mean() >= 0.9, (name, s, ok.mean())
     return float(ok.mean())
+
+
+# fp64 engine vs the fp64 restatement.  The engine differs from the
+# restatement only where it evaluates an expression differently: ocml instead
+# of glibc, exp(y log x) powers, square-root fourth roots, the Newton loops'
+# reciprocal division, tdfcnd's fused exp (oracle/noahmp_oracle.c
+# ORACLE_PERTURB lists the sites).  oracle/port.py step_ensemble runs the
+# restatement with each of those values moved within its device bound, 28
+# members; per column that gives `discrete` (a member changed ISNOW, status or
+# a loop trip count) and q (the largest member deviation in units of the bar).
+# One rule, no fractions:
+#  * a column that is not discrete has the base's ISNOW and status, and every
+#    value within FP64_BAR max(1, FP64_Q_MARGIN q) (1 + |base|).  The factor 2
+#    is the margin over the ensemble: the engine's fixed error pattern can
+#    exceed 28 random sign patterns.  For q <= 0.5 that is the plain bar.
+#  * discrete columns are named, stay inside the loop-exit envelope
+#    (FP64_STATE_ENV / FP64_DIAG_ENV), and number at most FP64_DISCRETE_FRAC of
+#    a fixture and FP64_DISCRETE_POOLED of all fixture columns pooled.
+FP64_BAR = 1e-9
+FP64_Q_MARGIN = 2.0
+FP64_DISCRETE_FRAC = 0.01
+FP64_DISCRETE_POOLED = 0.001
+
+
+def perturb_bounds() -> dict:
+    """Bounds in ulps of the perturbed restatement's site kinds: what
+    tests/test_gpu_math64.py asserts of the device functions (the recorded
+    maxima of profiles/math64/ulp.json plus its MARGIN; 1.5 / 2.5 for the
+    square-root fourth roots), 1 ulp for the reciprocal division
+    (tests/test_gpu_routines.py) and ocml's stated 1 ulp plus MARGIN for the
+    one double pow of the water-table routine."""
+    import json
+    from test_gpu_math64 import MARGIN, OCML, ULP_JSON
+    with open(ULP_JSON) as f:
+        m = json.load(f)["max_ulp"]
+    b = {fn: m[fn] + MARGIN for fn in OCML}
+    b.update(pow_q=1.5, pow_mq=2.5, div=1.0, pow_d=1.0 + MARGIN)
+    return b
+
+
+def bar_units(got, base) -> np.ndarray:
+    """|got - base| / (FP64_BAR (1 + |base|)) per element; identical elements
+    (NaN == NaN, inf == inf) are 0, a non-finite one against a finite one inf."""
+    got, base = np.asarray(got, np.float64), np.asarray(base, np.float64)
+    same = (got == base) | (np.isnan(got) & np.isnan(base))
+    with np.errstate(invalid="ignore", over="ignore"):
+        u = np.abs(got - base) / (FP64_BAR * (1.0 + np.abs(base)))
+    return np.where(same, 0.0, np.where(np.isnan(u), np.inf, u))
+
+
+def check_fp64_rule(what, groups, isn, status, base_isn, base_status, discrete, q, pool=None):
+    """The rule above.  groups: [(got(nf, n), base(nf, n), field names,
+    (rtol, atol) envelope)].  Prints and returns the record
+    {n, worst (in units of the column's tolerance), column, field, q_max,
+    discrete: [columns]}, appends it to `pool` (for check_fp64_pooled and the
+    envelope record) and asserts the rule."""
+    n = int(q.size)
+    scale = np.maximum(1.0, FP64_Q_MARGIN * np.asarray(q, np.float64))
+    ratio = np.zeros(n)
+    field = np.full(n, "", dtype=object)
+    env_ok = np.ones(n, bool)
+    for got, base, names, env in groups:
+        u = bar_units(got, base) / scale
+        k = u.argmax(axis=0)
+        best = u[k, np.arange(n)]
+        up = best > ratio
+        ratio = np.where(up, best, ratio)
+        field[up] = np.asarray(names, dtype=object)[k[up]]
+        env_ok &= close(got, base, *env).all(0)
+    held = ~discrete
+    flip = held & ((isn != base_isn) | (status != base_status))
+    masked = np.where(held, ratio, 0.0)
+    c = int(masked.argmax()) if n else 0
+    rec = dict(what=what, n=n, worst=float(masked[c]) if n else 0.0, column=c,
+               field=str(field[c]) if n else "", q_max=float(np.max(q)) if n else 0.0,
+               q_at_worst=float(q[c]) if n else 0.0,
+               discrete=[int(i) for i in np.nonzero(discrete)[0]])
+    print(f"{what}: worst {rec['worst']:.4f} of the tolerance at column {c} ({rec['field']}, "
+          f"q {rec['q_at_worst']:.3f}); q max {rec['q_max']:.3f}; discrete {rec['discrete']}")
+    if pool is not None:
+        pool.append(rec)
+    assert not flip.any(), f"{what}: ISNOW or status differs on held columns " \
+        f"{list(np.nonzero(flip)[0][:8])}"
+    over = held & ~(ratio <= 1.0)
+    assert not over.any(), \
+        f"{what}: {int(over.sum())} columns outside 1e-9 max(1, 2q)(1 + |x|): " + "; ".join(
+            f"col {i} {field[i]} {ratio[i]:.3g}x (q {q[i]:.3g})" for i in np.nonzero(over)[0][:8])
+    bad_env = discrete & ~env_ok
+    assert not bad_env.any(), f"{what}: discrete columns {list(np.nonzero(bad_env)[0][:8])} " \
+        "outside the loop-exit envelope"
+    assert discrete.sum() <= FP64_DISCRETE_FRAC * n, (what, rec["discrete"])
+    return rec
+
+
+def check_fp64_pooled(records):
+    """The pooled cap on discrete columns over records of check_fp64_rule, one
+    per column set (not one per kernel variant)."""
+    tot_n = sum(r["n"] for r in records)
+    tot_d = sum(len(r["discrete"]) for r in records)
+    print(f"fp64 discrete columns pooled: {tot_d} of {tot_n}")
+    assert tot_d <= FP64_DISCRETE_POOLED * tot_n, \
+        f"{tot_d} discrete columns of {tot_n} pooled: " + str(
+            [(r["what"], r["discrete"]) for r in records if r["discrete"]])
+
+
+def fixture_step_args(g: dict):
+    """port.step's positional arguments for a single-call fixture, with the
+    table values the fixture was generated with."""
+    return (fixture_params(g), tuple(g["options"]), g["zsoil"], float(g["dt"]), int(g["yearlen"]),
+            float(g["julian"]), g["state0"], g["isnow0"], g["static_f"], g["static_i"],
+            g["forcing"])
+
+
+_ENSEMBLES = {}
+
+
+def fixture_ensemble(port, fname: str):
+    """port.step_ensemble of the fixture file `fname` at amplitude 1, computed
+    once per session and shared (read-only) by every test that needs it."""
+    if fname not in _ENSEMBLES:
+        base, discrete, q = port.step_ensemble(*fixture_step_args(load(fname)), perturb_bounds())
+        for a in (*base, discrete, q):
+            a.setflags(write=False)
+        _ENSEMBLES[fname] = (base, discrete, q)
+    return _ENSEMBLES[fname]

@@ -16,18 +16,47 @@ libnoahmp_engine.so).  Two tiers:
    atanf are not correctly rounded) amplified by Newton iteration counts; the
    same bar is met by the CR oracle on the CPU (test_oracle_golden.py).
 
-fp64 engine vs the fp64 restatement: |d| <= 1e-9 (1 + |ref|) on >= 99 % of
-columns (ocml vs glibc double libm ulps).
+fp64 engine vs the fp64 restatement (oracle/noahmp_oracle.c, -DORACLE_DOUBLE):
+one rule on every column, golden_io.check_fp64_rule.  The restatement is run
+as an ensemble (oracle/port.py step_ensemble: the base and 28 members in which
+every value the fp64 kernel forms differently -- ocml's libm against glibc's,
+pow as exp(y log x), fourth roots as square roots, the Newton loops' reciprocal
+division, tdfcnd's fused exp -- is moved within the bound the device tests
+assert for it).  Per column that gives q, the largest member deviation in
+units of 1e-9 (1 + |x|), and `discrete`, whether a member changed ISNOW,
+status or a loop trip count.  A column that is not discrete must have the
+base's ISNOW and status and every value within 1e-9 max(1, 2 q) (1 + |x|);
+discrete columns are named, held to the loop-exit envelope and capped at 1 %
+of a fixture and 0.1 % pooled.  On the CPU (tests/test_fp64_envelope.py) no
+fixture column is discrete and q <= 0.91 (0.17 on the single-call fixtures),
+so all but one fixture column are held to the plain 1e-9 bar.  Measured on the
+MI355X: the engine's worst column is at 0.13 of its tolerance (config #5,
+rank 3), at most 0.036 on the fixtures, and no column is discrete.  Both occupancy
+kernels are compared (they come from two translation units), and must agree
+with each other bit for bit.  Running this file as a program writes each
+comparison's worst ratio to profiles/fp64/envelope.json (a record; nothing
+asserts against it).
 """
 import dataclasses
+import os
+import sys
+
+if __name__ == "__main__":   # as a program: the paths tests/conftest.py sets up
+    _root = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+    for _p in (_root, os.path.join(_root, "oracle"), os.path.join(_root, "tests")):
+        if _p not in sys.path:
+            sys.path.insert(0, _p)
+    import noahmp_pkg  # noqa: F401
 
 import numpy as np
 import pytest
 import torch
 
-from golden_io import (FP64_POOLED_FRAC, FP64_TOL_FRAC, as_ref_status, bit_equal,
-                       check_fp64_trajectory_step, close, column_mismatch, fixture_tags, load,
-                       load_params, parity_fp64_vs_reference, parity_vs_reference, single_names)
+from golden_io import (FP64_DIAG_ENV, FP64_POOLED_FRAC, FP64_STATE_ENV, FP64_TOL_FRAC,
+                       as_ref_status, bit_equal, check_fp64_pooled, check_fp64_rule,
+                       check_fp64_trajectory_step, close, column_mismatch, fixture_ensemble,
+                       fixture_params, fixture_step_args, fixture_tags, load, load_params,
+                       parity_fp64_vs_reference, parity_vs_reference, perturb_bounds, single_names)
 from noahmp_amd import cases, layout as L
 
 pytestmark = pytest.mark.gpu
@@ -43,8 +72,18 @@ VARIANTS = ["small", "full"]
 VARIANTS32 = VARIANTS
 
 
+# records of golden_io.check_fp64_rule made in this session (the envelope record)
+FP64_RECORDS = []
+ENVELOPE_JSON = os.path.join(os.path.dirname(os.path.dirname(os.path.abspath(__file__))),
+                             "profiles", "fp64", "envelope.json")
+
+
 @pytest.fixture(scope="module")
 def engines(engine_lib):
+    return _engine_cache()
+
+
+def _engine_cache():
     from noahmp_amd.engine import Engine
     from noahmp_amd.params import Params
     cache, tables = {}, {}
@@ -61,15 +100,16 @@ def engines(engine_lib):
     return get
 
 
-def run_single(eng, g, dtype=torch.float32):
+def run_single(eng, g, dtype=torch.float32, level=L.DIAG_FULL_LEVEL):
     from noahmp_amd.engine import ColumnState
     cols = cases.ColumnSet(g["static_f"], g["static_i"], g["state0"], g["isnow0"],
                            *([None] * 7))
     cs = ColumnState.from_host(cols, DEV, dtype)
     f = torch.as_tensor(g["forcing"], device=DEV).to(dtype).contiguous()
-    diag = torch.zeros((L.NDIAG_FULL, cs.ncol), dtype=dtype, device=DEV)
+    nd = L.NDIAG_FULL if level == L.DIAG_FULL_LEVEL else L.NDIAG_OUT
+    diag = torch.zeros((nd, cs.ncol), dtype=dtype, device=DEV)
     eng.step(cs, f, g["zsoil"], float(g["dt"]), float(g["julian"]), int(g["yearlen"]), diag,
-             L.DIAG_FULL_LEVEL)
+             level)
     torch.cuda.synchronize()
     return (cs.state.cpu().numpy(), cs.isnow.cpu().numpy(), diag.cpu().numpy(),
             cs.status.cpu().numpy())
@@ -110,17 +150,80 @@ def test_single_call_bit_exact_vs_reference(engines, name, variant):
             rep_s[:8] + rep_d[:8])
 
 
-@pytest.mark.parametrize("name", ["casenml_mixed", "casenml_conus", "veg2", "run3", "frz2",
-                                  "sfc2", "fatal"])
-def test_single_call_fp64_vs_fp64_oracle(engines, oracle_port, name):
+def fp64_single_records(get, port, name, pool):
+    """One single-call fixture through both fp64 occupancy kernels, each held
+    to the fixture's restatement ensemble: state, the 58 outputs and T2M (the
+    kernel's at the DIAG_OUT level, the restatement's through its hook)."""
     g = load(f"single_{name}.npz")
-    est, eisn, edg, estat = oracle_single(oracle_port, g, 8)
-    st, isn, dg, status = run_single(engines(g["options"], 8), g, torch.float64)
-    ok = close(st, est, 1e-9, 1e-9).all(0) & close(dg, edg, 1e-9, 1e-9).all(0) & \
-        (isn == eisn) & (status == estat)
-    _, rep_s = column_mismatch(st, est, 1e-9, 1e-9, STATE_NAMES)
-    _, rep_d = column_mismatch(dg, edg, 1e-9, 1e-9, L.DIAG_FULL)
-    assert ok.mean() >= 0.99 or (~ok).sum() <= 1, "; ".join(rep_s[:8] + rep_d[:8])
+    (est, eisn, edg, estat, _, et2m), discrete, q = fixture_ensemble(port, f"single_{name}.npz")
+    for variant in VARIANTS:
+        eng = get(g["options"], 8, tags=fixture_tags(g), variant=variant)
+        st, isn, dg, status = run_single(eng, g, torch.float64)
+        st2, isn2, out, status2 = run_single(eng, g, torch.float64, L.DIAG_OUT_LEVEL)
+        assert bit_equal(st2, st).all() and np.array_equal(isn2, isn)
+        t2m = out[L.DIAG_OUT.index("T2M")][None]
+        check_fp64_rule(f"single_{name}/{variant}",
+                        [(st, est, STATE_NAMES, FP64_STATE_ENV), (dg, edg, L.DIAG_FULL, FP64_DIAG_ENV),
+                         (t2m, et2m[None], ["T2M"], FP64_DIAG_ENV)],
+                        isn, status, eisn, estat, discrete, q, pool)
+
+
+@pytest.mark.parametrize("name", single_names())
+def test_single_call_fp64_vs_fp64_oracle(engines, oracle_port, name):
+    """Every column of every single-call fixture, with the fixture's own
+    tables, on both fp64 kernels: the module docstring's rule."""
+    fp64_single_records(engines, oracle_port, name, FP64_RECORDS)
+
+
+SMALL_FULL_FIXTURES = ["single_casenml_mixed", "single_veg2", "single_frz2", "single_fatal",
+                       "branch_combo"]
+
+
+@pytest.mark.parametrize("fname", SMALL_FULL_FIXTURES)
+def test_fp64_small_and_full_kernels_bit_equal(engine_lib, fname):
+    """The half- and full-occupancy fp64 kernels are built from two
+    translation units (sflx_kernel_f64s.hip, sflx_kernel_f64.hip); with
+    -ffp-contract=off and no fast-math on both, they must give the same bits:
+    state, the 58 outputs, ISNOW and status, on fixtures that cover snow,
+    frozen soil, carbon, the fatal statuses and the rare branches under
+    run-time options."""
+    from noahmp_amd.engine import Engine
+    from noahmp_amd.params import Params
+    g = load(fname + ".npz")
+    outs = []
+    for variant in VARIANTS:
+        eng = Engine(Params.from_dict(fixture_params(g)),
+                     dict(zip(L.OPTION_NAMES, (int(x) for x in g["options"]))), device=0,
+                     precision=8, math="ref")
+        try:
+            assert eng.launch_variant(variant) == variant
+            outs.append(run_single(eng, g, torch.float64))
+        finally:
+            eng.close()
+    (sa, ia, da, ta), (sb, ib, db, tb) = outs
+    diff = ~(bit_equal(sa, sb).all(0) & bit_equal(da, db).all(0) & (ia == ib) & (ta == tb))
+    _, rep_s = column_mismatch(sa, sb, 0, 0, STATE_NAMES)
+    _, rep_d = column_mismatch(da, db, 0, 0, L.DIAG_FULL)
+    assert not diff.any(), f"{fname}: {int(diff.sum())} columns differ between small and full " \
+        f"(first {list(np.nonzero(diff)[0][:8])}): " + "; ".join(rep_s[:8] + rep_d[:8])
+
+
+@pytest.mark.parametrize("variant", VARIANTS32)
+@pytest.mark.parametrize("name", single_names())
+def test_t2m_bit_exact_vs_restatement(engines, oracle_port, name, variant):
+    """NMP_O_T2M, the composite 2-m temperature (the fveg blend of T2MV and
+    T2MB, func.f90:1256/1270) that is not among the 58 full outputs: the fp32
+    kernel's value at the DIAG_OUT level equals the fp32 restatement's
+    (port.step_t2m; pinned to the reference's T2MV/T2MB/FVEG by
+    tests/test_fp64_envelope.py) bit for bit on every column."""
+    g = load(f"single_{name}.npz")
+    eng = engines(g["options"], tags=fixture_tags(g), variant=variant)
+    out = run_single(eng, g, level=L.DIAG_OUT_LEVEL)[2]
+    t2m = out[L.DIAG_OUT.index("T2M")]
+    want = oracle_port.step_t2m(*fixture_step_args(g), precision=4)[-1]
+    bad = ~bit_equal(t2m, want)
+    assert not bad.any(), (int(bad.sum()), [(int(i), float(t2m[i]), float(want[i]))
+                                            for i in np.nonzero(bad)[0][:8]])
 
 
 @pytest.mark.parametrize("variant", VARIANTS)
@@ -631,8 +734,9 @@ _SINGLE_FIXTURES = ["single_" + n for n in single_names()]
 @pytest.mark.parametrize("variant", VARIANTS)
 @pytest.mark.parametrize("name", _SINGLE_FIXTURES)
 def test_diag_levels_consistent(engines, name, variant, precision):
-    """DIAG_OUT fields are the DIAG_FULL values (T2M = the fveg blend of
-    T2MV/T2MB), and the state is the same bits at every diagnostics level --
+    """DIAG_OUT fields are the DIAG_FULL values (T2M, which DIAG_FULL lacks, is
+    pinned bit for bit by test_t2m_bit_exact_vs_restatement and held to the
+    fp64 rule by test_single_call_fp64_vs_fp64_oracle), and the state is the same bits at every diagnostics level --
     with no diagnostics the kernel skips the 2-m chain (MOZ2 -> FH2 -> CHV2,
     CHB2 -> T2M, Q2), which nothing else reads -- for every single-call
     fixture (every option value and table pair), on both occupancy kernels,
@@ -655,12 +759,6 @@ def test_diag_levels_consistent(engines, name, variant, precision):
     for i, n in enumerate(L.DIAG_OUT):
         if n != "T2M":
             np.testing.assert_array_equal(out[i], full[L.DIAG_FULL.index(n)], err_msg=n)
-    if name == "single_casenml_conus" and precision == 4:
-        fveg = full[L.DIAG_FULL.index("FVEG")]
-        t2m = out[L.DIAG_OUT.index("T2M")]
-        veg = g["static_i"][L.STATIC_I.index("IST")] == 1
-        blend = fveg * full[L.DIAG_FULL.index("T2MV")] + (1 - fveg) * full[L.DIAG_FULL.index("T2MB")]
-        np.testing.assert_allclose(t2m[veg & (fveg > 0)], blend[veg & (fveg > 0)], rtol=1e-5)
     for lvl in (L.DIAG_OUT_LEVEL, L.DIAG_NONE):
         assert bit_equal(outs[lvl][0], outs[L.DIAG_FULL_LEVEL][0]).all(), lvl
 
@@ -840,9 +938,29 @@ def test_full_size_sample_vs_oracle(engines, oracle_port, kind, ncol, opt_veg, p
     sample of 2,048 columns re-run through the C restatement (JULIAN is a real
     argument of noahmp_sflx and of nmp_step, fp32 in every precision, so the
     oracle gets the same fp32 value; the restatement is bit-exact to the
-    reference in fp32 on every fixture): bit-identical in fp32, |d| <= 1e-9
-    (1 + |x|) in fp64.  Column independence makes the sample a full check of
+    reference in fp32 on every fixture): bit-identical in fp32; in fp64 the
+    module docstring's rule against the restatement's ensemble over the two
+    steps (state, the output fluxes and T2M).  Column independence makes the sample a full check of
     those columns at full launch size (grid, stream ranges, ragged tail)."""
+    full_size_sample(engines, oracle_port, kind, ncol, opt_veg, precision, FP64_RECORDS)
+
+
+def _check_fp64_sample(what, port, opts, dt, yl, jul, forc, cols, idx, got, gd, gisn, gstatus,
+                       pool):
+    """The fp64 rule on sampled columns after len(jul) steps: the restatement's
+    ensemble with the forcing the device stepped them with; the state, the
+    output-level fluxes and T2M."""
+    (st, isn, dg, status, _, t2m), discrete, q = port.run_ensemble(
+        load_params(), tuple(opts[x] for x in L.OPTION_NAMES), cases.CASE_NML_ZSOIL, dt, yl,
+        [float(np.float32(j)) for j in jul], cols.state[:, idx], cols.isnow[idx],
+        cols.static_f[:, idx], cols.static_i[:, idx], [f[:, idx] for f in forc], perturb_bounds())
+    od = np.stack([t2m if n == "T2M" else dg[L.DIAG_FULL.index(n)] for n in L.DIAG_OUT])
+    return check_fp64_rule(what, [(got, st, STATE_NAMES, FP64_STATE_ENV),
+                                  (gd, od, L.DIAG_OUT, FP64_DIAG_ENV)],
+                           gisn, gstatus, isn, status, discrete, q, pool)
+
+
+def full_size_sample(engines, oracle_port, kind, ncol, opt_veg, precision, pool):
     from noahmp_amd.engine import ColumnState, StreamShards
     from noahmp_amd.params import Params
     P = Params.builtin()
@@ -862,23 +980,24 @@ def test_full_size_sample_vs_oracle(engines, oracle_port, kind, ncol, opt_veg, p
     torch.cuda.synchronize()
     idx = np.sort(np.random.default_rng(3).choice(ncol, 2048, replace=False))
     idx[-1] = ncol - 1  # the ragged tail's last column
+    got = cs.state.cpu().numpy()[:, idx]
+    gd = diag.cpu().numpy()[:, idx]
+    gisn = cs.isnow.cpu().numpy()[idx]
+    if precision == 8:
+        _check_fp64_sample(f"full_size/{kind}/{ncol}", oracle_port, opts, dt, 366, jul, F, cols, idx,
+                           got, gd, gisn, cs.status.cpu().numpy()[idx], pool)
+        return
     st, isn = cols.state[:, idx], cols.isnow[idx]
     for s in range(2):
         st, isn, dg, status = oracle_port.step(
             load_params(), tuple(opts[k] for k in L.OPTION_NAMES), cases.CASE_NML_ZSOIL, dt, 366,
             float(np.float32(jul[s])), st, isn, cols.static_f[:, idx], cols.static_i[:, idx], F[s][:, idx],
             precision=precision)
-    got = cs.state.cpu().numpy()[:, idx]
-    gd = diag.cpu().numpy()[:, idx]
     od = np.stack([dg[L.DIAG_FULL.index(n)] for n in L.DIAG_OUT if n != "T2M"])
     gd = np.stack([gd[i] for i, n in enumerate(L.DIAG_OUT) if n != "T2M"])
-    assert np.array_equal(cs.isnow.cpu().numpy()[idx], isn)
-    if precision == 4:
-        ok = bit_equal(got, st).all(0) & bit_equal(gd, od).all(0)
-        assert ok.all(), f"{(~ok).sum()} of {idx.size} sampled columns differ"
-    else:
-        ok = close(got, st, 1e-9, 1e-9).all(0) & close(gd, od, 1e-9, 1e-9).all(0)
-        assert ok.mean() >= 0.99, column_mismatch(got, st, 1e-9, 1e-9, STATE_NAMES)[1][:8]
+    assert np.array_equal(gisn, isn)
+    ok = bit_equal(got, st).all(0) & bit_equal(gd, od).all(0)
+    assert ok.all(), f"{(~ok).sum()} of {idx.size} sampled columns differ"
 
 
 @pytest.mark.parametrize("rank", [0, 3])
@@ -892,7 +1011,12 @@ def test_config5_shard_bench_pipeline_vs_oracle(engines, oracle_port, rank):
     emulated on one GPU (`--emulate-rank`).  Rank 0 is the polar band (ice
     sheets), rank 3 the southern subtropics.  Three steps, then a seeded
     sample of 2,048 columns through the fp64 restatement with the device's
-    forcing: |d| <= 1e-9 (1 + |x|) on >= 99 % of columns, state and fluxes."""
+    forcing, as an ensemble: the module docstring's rule on every sampled
+    column, state, fluxes and T2M."""
+    config5_shard(engines, oracle_port, rank, FP64_RECORDS)
+
+
+def config5_shard(engines, oracle_port, rank, pool):
     from noahmp_amd.engine import ColumnState, StreamShards
     from noahmp_amd.order import coherent_order
     from noahmp_amd.params import Params
@@ -920,20 +1044,24 @@ def test_config5_shard_bench_pipeline_vs_oracle(engines, oracle_port, rank):
         forc.append(f.cpu().numpy().copy())
     idx = np.sort(np.random.default_rng(7).choice(n, 2048, replace=False))
     idx[-1] = n - 1
-    st, isn = cols.state[:, idx], cols.isnow[idx]
-    for k in range(nsteps):
-        st, isn, dg, _ = oracle_port.step(
-            load_params(), tuple(opts[x] for x in L.OPTION_NAMES), cases.CASE_NML_ZSOIL, dt, yl,
-            float(np.float32(jul[k])), st, isn, cols.static_f[:, idx], cols.static_i[:, idx],
-            forc[k][:, idx], precision=8)
     got = cs.state.cpu().numpy()[:, idx]
     gd = diag.cpu().numpy()[:, idx]
-    od = np.stack([dg[L.DIAG_FULL.index(m)] for m in L.DIAG_OUT if m != "T2M"])
-    gd = np.stack([gd[i] for i, m in enumerate(L.DIAG_OUT) if m != "T2M"])
     assert np.isfinite(got[L.s("STC")]).all()
-    ok = close(got, st, 1e-9, 1e-9).all(0) & close(gd, od, 1e-9, 1e-9).all(0) & \
-        (cs.isnow.cpu().numpy()[idx] == isn)
-    assert ok.mean() >= 0.99, column_mismatch(got, st, 1e-9, 1e-9, STATE_NAMES)[1][:8]
+    _check_fp64_sample(f"config5_shard/rank{rank}", oracle_port, opts, dt, yl, jul, forc, cols, idx,
+                       got, gd, cs.isnow.cpu().numpy()[idx], cs.status.cpu().numpy()[idx], pool)
+
+
+def test_fp64_discrete_columns_pooled(oracle_port):
+    """The pooled cap of the fp64 rule: over every single-call and branch
+    fixture column (the ensembles the tests above share; computed here where
+    one has not run) and the full-size samples checked in this session, at
+    most 0.1 % of the columns are discrete.  Measured: none."""
+    from test_branch_golden import SINGLES as branch_names
+    recs = [r for r in FP64_RECORDS if r["what"].split("/")[0] in ("full_size", "config5_shard")]
+    for fname in ["single_" + n for n in single_names()] + ["branch_" + n for n in branch_names]:
+        _, discrete, q = fixture_ensemble(oracle_port, fname + ".npz")
+        recs.append(dict(what=fname, n=int(q.size), discrete=list(np.nonzero(discrete)[0])))
+    check_fp64_pooled(recs)
 
 
 def test_bench_window_bit_exact_vs_oracle(engines, oracle_port):
@@ -1231,3 +1359,59 @@ def test_full_size_year_sample_vs_reference(engines, cfg):
         ok = bit_equal(got, rec.st.T).all(0) & bit_equal(gd, od).all(0)
         assert ok.all(), f"chunk {c} (step {s0 + per}): {(~ok).sum()} of {idx.size} columns differ"
     assert (rec.isn < 0).any() or (cols.isnow[idx] < 0).any()  # snow came and went
+
+
+if __name__ == "__main__":
+    # measure every fp64 comparison on the device and write profiles/fp64/envelope.json
+    # (an optional argument names another output path)
+    import json
+    import subprocess
+    import port
+    import test_gpu_branches as tb
+    from noahmp_amd import build as _build, lib as _lib
+    if not all(port.available(k) for k in port.LIBS):
+        subprocess.run(["make", "-s", "-C", os.path.dirname(port.HERE) + "/oracle", "port"],
+                       check=True)
+    if _build.LIB_PATH == _build.DEFAULT_LIB_PATH:
+        _build.build()
+    _lib.load()
+    records, failed = [], []
+
+    def attempt(fn, *a):
+        try:
+            fn(*a, records)
+        except AssertionError as e:   # recorded, not hidden: the tests assert
+            failed.append(str(e)[:400])
+
+    get = _engine_cache()
+    for name in single_names():
+        attempt(fp64_single_records, get, port, name)
+    bget = tb.engine_cache()
+    bengines = next(bget)
+    for name in tb.SINGLES:
+        attempt(tb.fp64_branch_records, bengines, port, name)
+    attempt(full_size_sample, get, port, "global", 1_036_800, 2, 8)
+    attempt(full_size_sample, get, port, "casenml", 65536, 1, 8)
+    for rank in (0, 3):
+        attempt(config5_shard, get, port, rank)
+    try:
+        ver = open("/opt/rocm/.info/version").read().strip()
+    except OSError:
+        ver = subprocess.run(["hipconfig", "--version"], capture_output=True,
+                             text=True).stdout.strip()
+    path = sys.argv[1] if len(sys.argv) > 1 else ENVELOPE_JSON
+    os.makedirs(os.path.dirname(os.path.abspath(path)), exist_ok=True)
+    worst = max(records, key=lambda r: r["worst"])
+    with open(path, "w") as f:
+        json.dump({"what": "fp64 engine against the fp64 restatement's ensemble "
+                           "(golden_io.check_fp64_rule): per comparison the worst deviation of a "
+                           "held column in units of its tolerance 1e-9 max(1, 2 q) (1 + |x|), the "
+                           "column and field it occurs on, the ensemble's largest q and the "
+                           "discrete columns",
+                   "device": "MI355X (gfx950)", "rocm": ver,
+                   "worst": {k: worst[k] for k in ("what", "worst", "column", "field")},
+                   "columns": sum(r["n"] for r in records),
+                   "discrete_columns": sum(len(r["discrete"]) for r in records),
+                   "failed": failed, "records": records}, f, indent=1)
+        f.write("\n")
+    print(json.dumps({"worst": worst, "failed": failed}, indent=1))
