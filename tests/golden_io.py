@@ -37,6 +37,39 @@ def single_names() -> list[str]:
     return sorted(os.path.basename(p)[7:-4] for p in glob.glob(os.path.join(GOLDEN, "single_*.npz")))
 
 
+# Grouped fixtures (tests/golden/make_layers_golden.py): several launches in one
+# file, each with its own soil layering and time step.  zsoil (G, 4), dt,
+# yearlen, julian or julian0 (G,) are per group; group (ncol,) holds each
+# column's group number 1..G; the arrays below carry the columns on their last axis.
+GROUP_SCALARS = ("zsoil", "dt", "yearlen", "julian", "julian0")
+GROUP_COLUMNS = ("state0", "isnow0", "static_f", "static_i", "forcing", "state1", "isnow1", "diag",
+                 "status", "states", "isnows", "diags", "statuses")
+
+
+def layer_groups(g: dict) -> list[int]:
+    """The group numbers of a grouped fixture (1..G, as its generator's table counts them)."""
+    return list(range(1, g["zsoil"].shape[0] + 1))
+
+
+def layer_group(g: dict, k: int) -> dict:
+    """Group k (1..G) of a grouped fixture as a dict in the single-call (or
+    trajectory) format: its own zsoil (4,), scalar dt, yearlen and julian, and
+    the columns of the group."""
+    assert 1 <= k <= g["zsoil"].shape[0], k
+    cols = g["group"] == k
+    out = {}
+    for key, v in g.items():
+        if key == "group":
+            continue
+        if key in GROUP_SCALARS:
+            out[key] = v[k - 1]
+        elif key in GROUP_COLUMNS:
+            out[key] = np.ascontiguousarray(v[..., cols])
+        else:
+            out[key] = v
+    return out
+
+
 def bit_equal(a, b) -> np.ndarray:
     """Elementwise identical (NaN == NaN), per element."""
     a = np.asarray(a)
@@ -296,12 +329,15 @@ def fixture_step_args(g: dict):
 _ENSEMBLES = {}
 
 
-def fixture_ensemble(port, fname: str):
-    """port.step_ensemble of the fixture file `fname` at amplitude 1, computed
-    once per session and shared (read-only) by every test that needs it."""
-    if fname not in _ENSEMBLES:
-        base, discrete, q = port.step_ensemble(*fixture_step_args(load(fname)), perturb_bounds())
+def fixture_ensemble(port, fname: str, group: int | None = None):
+    """port.step_ensemble of the fixture file `fname` (of its group `group`,
+    for a grouped fixture) at amplitude 1, computed once per session and
+    shared (read-only) by every test that needs it."""
+    key = fname if group is None else (fname, group)
+    if key not in _ENSEMBLES:
+        g = load(fname) if group is None else layer_group(load(fname), group)
+        base, discrete, q = port.step_ensemble(*fixture_step_args(g), perturb_bounds())
         for a in (*base, discrete, q):
             a.setflags(write=False)
-        _ENSEMBLES[fname] = (base, discrete, q)
-    return _ENSEMBLES[fname]
+        _ENSEMBLES[key] = (base, discrete, q)
+    return _ENSEMBLES[key]

@@ -3,11 +3,13 @@
 
 Developer aid (no test runs it).  Builds oracle/noahmp_oracle.c with
 `-O0 --coverage` into a temporary directory, runs every single-call fixture
-once and every step of every trajectory fixture through it, then reads
+once (a grouped fixture: every group), and every step of every trajectory
+fixture through it, then reads
 `gcov -b`: line and branch percentages, the lines never executed and the
 branch directions never taken.  The parity claim of the project is only as
 wide as this coverage: a branch no reference-generated fixture takes is
-pinned to nothing (tests/golden/make_branch_golden.py exists to close those).
+pinned to nothing (tests/golden/make_branch_golden.py and make_layers_golden.py
+exist to close those).
 
   python tools/oracle_coverage.py                 # every fixture
   python tools/oracle_coverage.py --skip branch_  # without the branch_*.npz fixtures
@@ -31,9 +33,29 @@ for p in (ROOT, os.path.join(ROOT, "oracle"), os.path.join(ROOT, "tests")):
 
 import noahmp_pkg  # noqa: E402,F401
 import port  # noqa: E402
-from golden_io import GOLDEN, fixture_params, load  # noqa: E402
+from golden_io import GOLDEN, fixture_params, layer_group, layer_groups, load  # noqa: E402
 
 SRC = os.path.join(ROOT, "oracle", "noahmp_oracle.c")
+
+
+def run_launch(name, g):
+    """One single-call fixture (or group) once, or every step of a trajectory."""
+    P, opts = fixture_params(g), tuple(g["options"])
+    common = (g["zsoil"], float(g["dt"]), int(g["yearlen"]))
+    if "states" in g:
+        st, isn = g["state0"], g["isnow0"]
+        for s in range(g["forcing"].shape[0]):
+            # the day each fixture's generator and test give step s (fp32 arithmetic
+            # for the branch and layers trajectories, as the engine's time loop advances it)
+            if name.startswith(("branch_", "layers_")):
+                jul = float(g["julian0"] + np.float32(s) * g["dt"] / np.float32(86400.0))
+            else:
+                jul = float(g["julian0"]) + s * float(g["dt"]) / 86400.0
+            st, isn, _, _ = port.step(P, opts, *common, jul, st, isn, g["static_f"],
+                                      g["static_i"], g["forcing"][s])
+    else:
+        port.step(P, opts, *common, float(g["julian"]), g["state0"], g["isnow0"],
+                  g["static_f"], g["static_i"], g["forcing"])
 
 
 def run_fixtures(skip):
@@ -45,22 +67,10 @@ def run_fixtures(skip):
         g = load(name)
         if "state0" not in g:
             continue
-        P, opts = fixture_params(g), tuple(g["options"])
-        common = (g["zsoil"], float(g["dt"]), int(g["yearlen"]))
-        if "states" in g:
-            st, isn = g["state0"], g["isnow0"]
-            for s in range(g["forcing"].shape[0]):
-                # the day each fixture's generator and test give step s (fp32 arithmetic
-                # for the branch trajectory, as the engine's time loop advances it)
-                if name.startswith("branch_"):
-                    jul = float(g["julian0"] + np.float32(s) * g["dt"] / np.float32(86400.0))
-                else:
-                    jul = float(g["julian0"]) + s * float(g["dt"]) / 86400.0
-                st, isn, _, _ = port.step(P, opts, *common, jul, st, isn, g["static_f"],
-                                          g["static_i"], g["forcing"][s])
-        else:
-            port.step(P, opts, *common, float(g["julian"]), g["state0"], g["isnow0"],
-                      g["static_f"], g["static_i"], g["forcing"])
+        # a grouped fixture (tests/golden/make_layers_golden.py) is several launches,
+        # each with its own zsoil, dt, yearlen and julian
+        for q in ([layer_group(g, k) for k in layer_groups(g)] if "group" in g else [g]):
+            run_launch(name, q)
         n += 1
     return n
 
