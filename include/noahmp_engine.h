@@ -31,7 +31,9 @@
  *                             over the columns of each region (basin means), on the device
  * nmp_ldasin_regrid,          no counterpart: an LDASIN file on its own (coarse) grid onto the
  *   nmp_ldasin_downscale      columns, and its elevation (lapse-rate) correction, on the device
- * nmp_frh2o, nmp_frh2o_host   frh2o (public routine)        core/module_noahmp_func.f90:4494-4598
+ * nmp_ldasin_cosz,            no counterpart: the forcing of a step between two input times
+ *   nmp_forcing_from_ldasin_interp  from the two resident blocks at the interval's ends
+ * nmp_frh2o, nmp_frh2o_host   frh2o (public routine)       core/module_noahmp_func.f90:4494-4598
  * nmp_calhum, nmp_calhum_host calhum (public by default)     core/module_noahmp_func.f90:3958-3984
  * nmp_state_from_aos          layout bridge from noahmp_state_t records
  *                                                           core/module_noahmp_type.f90:10-42
@@ -436,6 +438,73 @@ int nmp_ldasin_regrid(nmp_engine* eng, int64_t ncol, int64_t ld, int64_t npts,
                       uint32_t nearest_mask, float* ldasin, void* stream);
 int nmp_ldasin_downscale(nmp_engine* eng, int64_t ncol, int64_t ld, const float* dz, double lapse,
                          float* ldasin, void* stream);
+
+/* Forcing between input times (no counterpart in the reference, which has no
+ * forcing reader): the 12 NMP_A_* fields of the step that starts at t,
+ * t0 <= t < t1, from the two resident LDASIN blocks of the input times t0
+ * (ldasin0) and t1 (ldasin1), both fp32 with leading dimension ld like
+ * nmp_forcing_from_ldasin_geo's, possibly offset by a range's first column.
+ * The operation order below is part of this interface: the result's bits
+ * depend on the two blocks, the weight and the step's COSZ alone, and a host
+ * can restate them (noahmp-1_amd/tinterp.py interp_host).  All arithmetic is
+ * IEEE double, each operation rounded once (no fused multiply-add); each
+ * result is rounded once to fp32 and that fp32 value is widened to the engine
+ * precision, as nmp_forcing_from_ldasin does.
+ *  - weights: w1 = (t - t0) / (t1 - t0), formed by the caller in double,
+ *    0 <= w1 < 1; w0 = 1.0 - w1 is formed once on the host side of the call
+ *    and is what the kernel uses.
+ *  - w1 == 0.0: the result is nmp_forcing_from_ldasin_geo(ldasin0, ...) bit
+ *    for bit in all 12 fields, SWDOWN included; ldasin1 is not read and may be
+ *    NULL (NaNs in it cannot leak).
+ *  - COSZ (NMP_A_COSZ) = (float)(sin_lat*sin_decl + (cos_lat*cos_decl) *
+ *    cos((ha0 + lon) - pi)): nmp_forcing_from_ldasin_geo's expression, operation
+ *    order, geo layout and solar terms, at the step's own time t.
+ *  - a plain variable v (T2D, Q2D, U2D, V2D, PSFC, LWDOWN, and RAINRATE and
+ *    SWDOWN when not treated otherwise below), a and b its fp32 values in
+ *    blocks 0 and 1: x = (double)a*w0 + (double)b*w1 -- two rounded products,
+ *    then one add, in that order; the row gets (float)x.
+ *  - a held variable (bit v of hold_mask, v < NMP_L_COSZ; e.g. 1u <<
+ *    NMP_L_RAINRATE, an interval rate): block 0's bits, unchanged; block 1's
+ *    row of it is never loaded.
+ *  - SWDOWN with sw_zenith != 0 and its bit not in hold_mask: with czt =
+ *    (double)COSZ, the fp32 value above widened, cz0 and cz1 the two blocks'
+ *    NMP_L_COSZ rows widened to double (nmp_ldasin_cosz writes them), sw0 and
+ *    sw1 the blocks' SWDOWN and floor = cosz_floor:
+ *      m0 = cz0 > floor ? cz0 : floor        m1 = cz1 > floor ? cz1 : floor
+ *      k0 = (double)sw0 / m0                 k1 = (double)sw1 / m1
+ *      k  = k0*w0 + k1*w1                    (two products, then one add)
+ *      sw = czt > 0 ? czt*k : 0.0            rounded once to fp32
+ *    A NaN czt, cz0 or cz1 fails its comparison: a NaN czt gives 0.0, a NaN
+ *    cz0 or cz1 takes the floor.  Working from the fp32-rounded COSZ values is
+ *    deliberate: the device's double cosine is not correctly rounded, and a
+ *    host that is given the three COSZ rows still reproduces every bit.
+ *    cosz_floor (in (0, 1]; the offline driver's default is 0.05) bounds the
+ *    clearness ratio sw/cz at sunrise and sunset; it is a setting, not a
+ *    measurement.  Where both end points are darker than the floor and the
+ *    files' SWDOWN is 0 the result is 0.  With sw_zenith == 0 SWDOWN is a plain
+ *    variable and the blocks' NMP_L_COSZ rows are not read.
+ *  - SFCPRS = PSFC = the interpolated fp32 PSFC; CO2AIR = (float)(395e-6 *
+ *    (double)PSFC) and O2AIR = (float)(0.209 * (double)PSFC) from that fp32
+ *    value, as nmp_forcing_from_ldasin derives them from the file's.
+ * Device pointers, one kernel enqueued on `stream` (one double cosine per
+ * column).  NMP_E_ARG, with nothing enqueued and the outputs untouched, for
+ * ld < ncol, w1 outside [0, 1) or NaN, a hold_mask bit at or above NMP_L_COSZ,
+ * sw_zenith with cosz_floor outside (0, 1] or NaN, a NULL ldasin0, geo or
+ * forcing, or a NULL ldasin1 with w1 != 0; ncol == 0 is NMP_OK with nothing
+ * enqueued.
+ *
+ * nmp_ldasin_cosz writes row NMP_L_COSZ of a resident block: COSZ at the
+ * block's own input time, by the expression above from the same geo and that
+ * time's solar terms -- one cosine per column per input interval.  The other
+ * rows and the columns ncol..ld-1 are untouched.  NMP_E_ARG for ld < ncol or a
+ * NULL geo or ldasin; ncol == 0 is NMP_OK. */
+int nmp_ldasin_cosz(nmp_engine* eng, int64_t ncol, int64_t ld, const double* geo, double sin_decl,
+                    double cos_decl, double ha0, float* ldasin, void* stream);
+int nmp_forcing_from_ldasin_interp(nmp_engine* eng, int64_t ncol, int64_t ld,
+                                   const float* ldasin0, const float* ldasin1, double w1,
+                                   uint32_t hold_mask, int sw_zenith, double cosz_floor,
+                                   const double* geo, double sin_decl, double cos_decl, double ha0,
+                                   void* forcing, void* stream);
 
 /* The output side's mirror: nfield diagnostics of ncol columns (engine
  * precision, field-major, leading dimension ld -- e.g. the NMP_O_* fluxes of

@@ -125,7 +125,9 @@ class OfflineDriver:
                  streams: int = 2, grid: ncio.Grid | None = None, ldasin_upload: bool = True,
                  cosz: str = "device", ingest: bool = True, accumulate: bool = False,
                  regions=None, region_weights="area", write_grids: bool = True,
-                 downscale: bool = False, lapse_rate: float = 0.0065):
+                 downscale: bool = False, lapse_rate: float = 0.0065, interp: bool = False,
+                 hold=("RAINRATE",), sw_zenith: bool = True, cosz_floor: float = 0.05,
+                 prefetch: bool = True):
         """cols: this rank's columns (all of them on a single rank); under an
         initialised process group they must be the rank's shard_range block of
         the global column set.  ldasin_upload: with a provider that has
@@ -161,11 +163,31 @@ class OfflineDriver:
         resident LDASIN block on the device for the elevation difference
         between the model terrain and the source grid (nmp_ldasin_downscale,
         lapse_rate in K/m), on the upload stream right after the block is
-        formed there or uploaded; needs ldasin_upload and cosz="device"."""
+        formed there or uploaded; needs ldasin_upload and cosz="device".
+        interp: with LDASIN files as resident blocks, the steps between two
+        input times take their forcing from both files (feeds.LdasinInterpFeed,
+        nmp_forcing_from_ldasin_interp; tinterp.py states the scheme) instead
+        of holding the earlier file's values: linear in time, except the
+        variables named in `hold` (block 0's values; RAINRATE is an interval
+        rate) and SWDOWN, which with sw_zenith follows the step's own COSZ
+        through the end points' clearness ratios SWDOWN / max(COSZ, cosz_floor)
+        (sw_zenith=False: linear like the others).  The last interval runs
+        held when the file at its end does not exist (`interp_held`).
+        prefetch=False forms every block at the step that first needs it
+        instead of reading ahead.  Refused with cosz="host",
+        ldasin_upload=False, a provider without files or device-synthetic
+        forcing.  Off (the default), every code path and output byte is as
+        without it."""
         if not write_grids and regions is None:
             raise ValueError("write_grids=False needs regions: the run would write nothing")
-        # (a bad cosz or downscale is refused before any device work)
-        kind = feed_kind(forcing, ldasin_upload, cosz, ingest, downscale)
+        # (a bad cosz, downscale or interp is refused before any device work)
+        kind = feed_kind(forcing, ldasin_upload, cosz, ingest, downscale, interp)
+        iopts = None
+        if interp:
+            from . import tinterp
+            tinterp.check_args(0.0, tinterp.hold_mask(hold), sw_zenith, cosz_floor)
+            iopts = dict(ingest=ingest, hold=tuple(hold), sw_zenith=sw_zenith,
+                         cosz_floor=cosz_floor, end=cfg.enddatetime, prefetch=prefetch)
         dz_host = forcing.dz() if downscale else None  # ValueError without HGT and HGT_M
         self.cfg, self.grid = cfg, grid
         # from_files: the land point of each column of the whole set, and of this rank's
@@ -201,7 +223,8 @@ class OfflineDriver:
         # the 12-field host form, which every run has, and the run's own path
         host = HostFeed(self.forcing, self.cs.ncol, self.dtype, self.dev, bool(downscale))
         feed = self.feed = make_feed(kind, host, self.engine, self.cs.ncol, self.dtype, self.dev,
-                                     float(lapse_rate), dz_host)
+                                     float(lapse_rate), dz_host, iopts)
+        self.interp = bool(interp)
         self.upload, self.raw_upload, self.raw_fbuf = host.upload, feed.raw_upload, feed.raw_fbuf
         self.geo, self.ingest, self.point = feed.geo, feed.ingest, feed.point
         self.regrid_plan, self.dz = feed.regrid_plan, feed.dz
@@ -286,6 +309,12 @@ class OfflineDriver:
             if a is not None:  # a restart written part way through an interval
                 drv.accum.restore(a, idx)
         return drv
+
+    @property
+    def interp_held(self) -> list:
+        """The input times whose interval ran held although interp is on: the
+        closing interval of a run without a file at its end (noted once each)."""
+        return getattr(self.feed, "interp_held", [])
 
     def to_grid_order(self, a: np.ndarray) -> np.ndarray:
         """(..., n) columns of the whole set in engine order -> land-point order."""

@@ -307,6 +307,50 @@ class Engine:
                                                   _ptr(block, 0), C.c_void_p(s.cuda_stream)),
                    "nmp_ldasin_downscale")
 
+    def ldasin_cosz(self, block: torch.Tensor, geo: torch.Tensor,
+                    solar: tuple[float, float, float], stream=None,
+                    cols: tuple[int, int] | None = None):
+        """nmp_ldasin_cosz: row COSZ of the (NLDASIN, n) fp32 block := COSZ at
+        the block's own input time, from geo (3, n) float64 and solar =
+        timeman.solar_terms of that time; the other rows are untouched.
+        cols=(lo, hi) writes only those columns."""
+        n = int(block.shape[1])
+        lo, hi = self._cols_range(n, cols)
+        self._check_block(block, (L.NLDASIN, n), torch.float32, "block")
+        self._check_block(geo, (3, n), torch.float64, "geo")
+        sd, cd, ha0 = (float(v) for v in solar)
+        s = stream if stream is not None else torch.cuda.current_stream(self.device)
+        _lib.check(self._lib.nmp_ldasin_cosz(self._h, hi - lo, n, _ptr(geo, lo), sd, cd, ha0,
+                                             _ptr(block, lo), C.c_void_p(s.cuda_stream)),
+                   "nmp_ldasin_cosz")
+
+    def forcing_from_ldasin_interp(self, ldasin0: torch.Tensor, ldasin1: torch.Tensor | None,
+                                   w1: float, out: torch.Tensor, geo: torch.Tensor,
+                                   solar: tuple[float, float, float], hold_mask: int = 0,
+                                   sw_zenith: bool = True, cosz_floor: float = 0.05, stream=None,
+                                   cols: tuple[int, int] | None = None):
+        """nmp_forcing_from_ldasin_interp: the 12 forcing fields of the step
+        that starts a fraction w1 (0 <= w1 < 1) into an input interval, into
+        out (NFORCING, n), engine precision, from the interval's two resident
+        (NLDASIN, n) fp32 blocks (their COSZ rows written by ldasin_cosz);
+        tinterp.interp_host is the numpy form.  geo, solar: the step's own, as
+        in forcing_from_ldasin.  hold_mask: bit v = variable v keeps block 0's
+        value (tinterp.hold_mask).  ldasin1 may be None when w1 == 0.
+        cols=(lo, hi) forms only those columns."""
+        n = int(ldasin0.shape[1])
+        lo, hi = self._cols_range(n, cols)
+        self._check_block(ldasin0, (L.NLDASIN, n), torch.float32, "ldasin0")
+        if ldasin1 is not None:
+            self._check_block(ldasin1, (L.NLDASIN, n), torch.float32, "ldasin1")
+        self._check_block(out, (L.NFORCING, n), self.dtype, "out")
+        self._check_block(geo, (3, n), torch.float64, "geo")
+        sd, cd, ha0 = (float(v) for v in solar)
+        s = stream if stream is not None else torch.cuda.current_stream(self.device)
+        _lib.check(self._lib.nmp_forcing_from_ldasin_interp(
+            self._h, hi - lo, n, _ptr(ldasin0, lo), _ptr(ldasin1, lo), float(w1), int(hold_mask),
+            int(bool(sw_zenith)), float(cosz_floor), _ptr(geo, lo), sd, cd, ha0, _ptr(out, lo),
+            C.c_void_p(s.cuda_stream)), "nmp_forcing_from_ldasin_interp")
+
     def ldasout_grid(self, diag: torch.Tensor, point: torch.Tensor, out: torch.Tensor,
                      fill: float, stream=None):
         """nmp_ldasout_grid: the (nfield, n) diagnostics `diag` (engine

@@ -30,6 +30,10 @@ cosz="host" uploads the variables plus the host's COSZ every step
 (ncio.LdasinForcing.raw, nmp_forcing_from_ldasin); the 12-field host form
 (48 B per column, 96 in fp64) remains for providers that supply all of them,
 and for the steps of an input file that carries CO2AIR / O2AIR of its own.
+interp=True (LdasinInterpFeed) keeps the blocks of both ends of the input
+interval resident and each range forms its fields between them
+(nmp_forcing_from_ldasin_interp, tinterp.py) instead of holding the earlier
+file's values.
 """
 from __future__ import annotations
 
@@ -141,17 +145,23 @@ class DeviceSyntheticForcing:
 
 # ---- feeds --------------------------------------------------------------------------
 def feed_kind(forcing, ldasin_upload: bool = True, cosz: str = "device", ingest: bool = True,
-              downscale: bool = False) -> str:
+              downscale: bool = False, interp: bool = False) -> str:
     """The forcing path of a run, from the driver's `forcing` argument (a
     provider, "device" or None) and its arguments: "host" (12 fields from the
     host), "device-synth", "ldasin-step" (the LDASIN block with the host's
     COSZ every step), or a resident block per input file, built on the host
     ("ldasin-block") or from the file's bytes on the device ("ldasin-ingest";
-    "ldasin-regrid" for files on a grid of their own).  The one place that
-    asks the provider what it can do; no device work."""
+    "ldasin-regrid" for files on a grid of their own).  interp: the steps
+    between two input times interpolate between their resident blocks
+    ("ldasin-interp" wherever one of the three block kinds would have been
+    returned; any other path is refused).  The one place that asks the
+    provider what it can do; no device work."""
     if cosz not in ("device", "host"):
         raise ValueError(f"cosz must be 'device' or 'host', not {cosz!r}")
     files = ldasin_upload and hasattr(forcing, "raw")
+    if interp and not (files and cosz == "device"):
+        raise ValueError("interp needs LDASIN files uploaded as resident blocks with COSZ formed "
+                         "on the device (a file provider, ldasin_upload=True, cosz='device')")
     if downscale:
         if not (files and cosz == "device"):
             raise ValueError("downscale needs LDASIN files uploaded as resident blocks "
@@ -164,6 +174,8 @@ def feed_kind(forcing, ldasin_upload: bool = True, cosz: str = "device", ingest:
         return "host"
     if cosz == "host":
         return "ldasin-step"
+    if interp:
+        return "ldasin-interp"
     if not (ingest and hasattr(forcing, "grid_raw")):
         return "ldasin-block"
     return "ldasin-ingest" if getattr(forcing, "plan", None) is None else "ldasin-regrid"
@@ -389,11 +401,236 @@ class LdasinBlockFeed(LdasinStepFeed):
         self.blocks[nxt] = self._put_block(nxt, False)
 
 
+class LdasinInterpFeed(_Feed):
+    """Interpolation between input times (tinterp.py; nmp_forcing_from_ldasin_interp):
+    the steps of the input interval [ti, ti + every) read the resident blocks
+    of both its ends.  A block is formed per file exactly as LdasinBlockFeed
+    forms it, on the upload stream -- ingest or regrid from the file's bytes
+    (or the host's block, ingest=False), nmp_ldasin_downscale if asked, then
+    nmp_ldasin_cosz (COSZ at the file's own time, for the zenith-weighted
+    SWDOWN), then the block's event -- and each range forms its 12 fields on
+    its own stream before its launch, waiting on both blocks' events.
+
+    Three slots: the interval's two blocks are in use while the block after
+    them is read ahead (a thread fills the pinned slot; `launched` uploads it
+    once the bytes are there).  A device slot is overwritten only after the
+    events of the launches that read it, a pinned slot only after its upload's
+    (ForcingUpload); a read-ahead that is not used is waited for before its
+    slot is filled again.  prefetch=False forms every block at the step that
+    first needs it instead.
+
+    The interval whose closing file does not exist runs held (w1 = 0) when it
+    ends at or after the run's end (`end`), noted in `interp_held`; a missing
+    file anywhere else is a FileNotFoundError at the step that needs it."""
+    kind = "ldasin-interp"
+    NSLOT = 3
+
+    def __init__(self, host: HostFeed, engine, ncol: int, dtype, dev, lapse_rate: float = 0.0065,
+                 dz_host=None, ingest: bool = True, hold=("RAINRATE",), sw_zenith: bool = True,
+                 cosz_floor: float = 0.05, end: datetime.datetime | None = None,
+                 prefetch: bool = True):
+        from . import tinterp
+        self.host, self.forcing, self.engine = host, host.forcing, engine
+        self.hold_mask = tinterp.hold_mask(hold)
+        self.sw_zenith, self.cosz_floor = bool(sw_zenith), float(cosz_floor)
+        tinterp.check_args(0.0, self.hold_mask, self.sw_zenith, self.cosz_floor)
+        self.end, self.prefetch, self.lapse_rate = end, bool(prefetch), lapse_rate
+        self.blocks, self.interp_held = {}, []
+        self.read_ahead = 0  # blocks formed beside the steps, ahead of the one that needs them
+        self._prefetch, self._prefetch_pool = None, None
+        fr = self.forcing
+        if dz_host is not None:  # downscale
+            self.dz = torch.as_tensor(dz_host, device=dev).contiguous()
+        self.geo = torch.as_tensor(fr.geo(), device=dev).contiguous()
+        self.fbuf = torch.empty((2, L.NFORCING, ncol), dtype=dtype, device=dev)
+        if ingest and hasattr(fr, "grid_raw"):
+            regrid = getattr(fr, "plan", None) is not None
+            npts = fr.plan.npts if regrid else fr.grid.shape[0] * fr.grid.shape[1]
+            self.ingest = ForcingUpload(npts, torch.int32, dev, nbuf=self.NSLOT,
+                                        nfield=L.NLDASIN - 1)
+            self.ingest_blk = torch.zeros((self.NSLOT, L.NLDASIN, ncol), dtype=torch.float32,
+                                          device=dev)
+            if regrid:
+                self.regrid_plan = fr.plan.to(dev)
+            else:
+                self.point = torch.as_tensor(fr.point(), device=dev)
+            self.up = self.ingest
+        else:  # the host builds each block; the upload's device buffers are the slots
+            self.raw_upload = ForcingUpload(ncol, torch.float32, dev, nbuf=self.NSLOT,
+                                            nfield=L.NLDASIN)
+            self.up = self.raw_upload
+
+    # ---- files ---------------------------------------------------------------------
+    def _path(self, ti):
+        from .ncio import ldasin_path
+        return ldasin_path(self.forcing.indir, ti)
+
+    def _check_file(self, ti):
+        """The input file of ti can become a resident block (FileNotFoundError
+        naming it when it does not exist)."""
+        fr = self.forcing
+        own = {"COSZ", "CO2AIR", "O2AIR"} & fr.variables(ti)
+        if own:
+            raise ValueError(f"interp: {self._path(ti)} carries {', '.join(sorted(own))} of its "
+                             "own; interpolation between input times takes files with the 8 "
+                             "LDASIN variables only")
+        if not fr.ingestible(ti):
+            raise ValueError(f"interp: {self._path(ti)} does not hold the 8 LDASIN variables as "
+                             "fp32 grids of the forcing's shape; interpolation needs resident "
+                             "blocks")
+
+    def read(self, t0):
+        """The headers of the interval's files (cached per input time)."""
+        import os
+        fr = self.forcing
+        ti = fr.input_time(t0)
+        self._check_file(ti)
+        if t0 != ti and os.path.isfile(self._path(ti + fr.every)):
+            self._check_file(ti + fr.every)
+        return None
+
+    # ---- blocks --------------------------------------------------------------------
+    def _drop_prefetch(self):
+        """A read-ahead nobody takes finishes before its pinned slot is filled again."""
+        if self._prefetch is not None:
+            self._prefetch[1].exception()
+        self._prefetch = None
+
+    def _put_block(self, ti):
+        """Upload and form the block of input time ti in the next slot; returns
+        (device block, its event, its slot)."""
+        fr, up = self.forcing, self.up
+        self._check_file(ti)
+        if self.ingest is not None:
+            ready = False
+            if self._prefetch is not None and self._prefetch[0] == ti:
+                ready = self._prefetch[1].exception() is None
+                self._prefetch = None
+            else:
+                self._drop_prefetch()
+            g = up.put(fill=lambda h: fr.grid_raw(ti, out=h), prefilled=ready)
+            blk = self.ingest_blk[up.last_slot]
+            if self.regrid_plan is not None:
+                self.engine.ldasin_regrid(g, self.regrid_plan, blk, fr.nearest_mask,
+                                          stream=up.stream)
+            else:
+                self.engine.ldasin_ingest(g, self.point, blk, stream=up.stream)
+        else:
+            blk = up.put(fill=lambda h: fr.block(ti, out=h))
+        if self.dz is not None:
+            self.engine.ldasin_downscale(blk, self.dz, self.lapse_rate, stream=up.stream)
+        solar = timeman.solar_terms(timeman.julian(ti), timeman.yearlen(ti.year))
+        self.engine.ldasin_cosz(blk, self.geo, solar, stream=up.stream)
+        ev = torch.cuda.Event()
+        ev.record(up.stream)
+        return blk, ev, up.last_slot
+
+    def _block(self, ti):
+        if ti not in self.blocks:
+            self.blocks[ti] = self._put_block(ti)
+        return self.blocks[ti]
+
+    def step(self, k, t0, cur):
+        import os
+        from . import tinterp
+        fr = self.forcing
+        ti = fr.input_time(t0)
+        tn = ti + fr.every
+        for old in [b for b in self.blocks if b < ti]:
+            del self.blocks[old]
+        w1 = tinterp.weights(t0, ti, fr.every)[1]
+        b0, e0, s0 = self._block(ti)
+        b1, e1, s1 = None, None, None
+        if w1 != 0.0 and tn not in self.blocks and not os.path.isfile(self._path(tn)):
+            if self.end is None or tn < self.end:
+                raise FileNotFoundError(self._path(tn))
+            if ti not in self.interp_held:  # the closing interval runs held
+                self.interp_held.append(ti)
+            w1 = 0.0
+        if w1 != 0.0:
+            b1, e1, s1 = self._block(tn)
+        solar = timeman.solar_terms(timeman.julian(t0), timeman.yearlen(t0.year))
+        f = self.fbuf[k % 2]
+        pre = lambda st, rng: self.engine.forcing_from_ldasin_interp(  # noqa: E731
+            b0, b1, w1, f, self.geo, solar, self.hold_mask, self.sw_zenith, self.cosz_floor,
+            stream=st, cols=rng)
+        self._slots = (s0,) if s1 is None else (s0, s1)
+        self.last = FeedStep(f, pre, (cur, e0) if e1 is None else (cur, e0, e1), None, None)
+        return self.last
+
+    def launched(self, t0, producers):
+        """The step's launches read its blocks' slots; then the read-ahead."""
+        evs = []
+        for s in producers:
+            e = torch.cuda.Event()
+            e.record(s)
+            evs.append(e)
+        for slot in self._slots:
+            self.up.consumed[slot] = tuple(evs)
+        if self.prefetch:
+            self._read_ahead(t0)
+
+    def _read_ahead(self, t0):
+        """The first block after t0's that is not resident yet, among this
+        interval's closing block and the one after it (the third slot): start
+        reading its bytes, or -- once they are there -- upload and form it
+        beside the steps.  A file that is missing or cannot become a block is
+        left to the step that needs it."""
+        import os
+        fr = self.forcing
+        tn = fr.input_time(t0) + fr.every
+        nxt = tn if tn not in self.blocks else tn + fr.every
+        if nxt in self.blocks:
+            return
+        if self.ingest is None:
+            try:
+                if os.path.isfile(self._path(nxt)):
+                    self.blocks[nxt] = self._put_block(nxt)
+                    self.read_ahead += 1
+            except ValueError:
+                pass
+            return
+        pf = self._prefetch
+        if pf is None:
+            if os.path.isfile(self._path(nxt)):
+                try:
+                    self._check_file(nxt)
+                except ValueError:
+                    return
+                if self._prefetch_pool is None:
+                    from concurrent.futures import ThreadPoolExecutor
+                    self._prefetch_pool = ThreadPoolExecutor(1)
+                self._prefetch = (nxt, self.up.prefetch(lambda h: fr.grid_raw(nxt, out=h),
+                                                        self._prefetch_pool))
+            return
+        if not pf[1].done():
+            return
+        if pf[0] != nxt or pf[1].exception() is not None:
+            self._prefetch = None  # (finished: its slot is free for the next read)
+            return
+        try:
+            self.blocks[nxt] = self._put_block(nxt)
+            self.read_ahead += 1
+        except ValueError:
+            self._prefetch = None  # (done: nothing to wait for)
+
+    def reset(self):
+        """The resident blocks and the read-ahead belong to the old time; the
+        restart's interval rebuilds both its blocks (the weights depend on
+        time alone)."""
+        self.blocks.clear()
+        self._drop_prefetch()
+
+
 def make_feed(kind: str, host: HostFeed, engine, ncol: int, dtype, dev, lapse_rate: float = 0.0065,
-              dz_host=None):
-    """The feed of `kind` (feed_kind) around the run's HostFeed."""
+              dz_host=None, interp: dict | None = None):
+    """The feed of `kind` (feed_kind) around the run's HostFeed; interp: the
+    LdasinInterpFeed's own arguments."""
     if kind == "host":
         return host
+    if kind == "ldasin-interp":
+        return LdasinInterpFeed(host, engine, ncol, dtype, dev, lapse_rate, dz_host,
+                                **(interp or {}))
     if kind == "device-synth":
         return DeviceSynthFeed(host.forcing, engine, ncol, dtype, dev)
     if kind == "ldasin-step":

@@ -105,6 +105,11 @@ def load(build_if_missing: bool = False):
     lib.nmp_ldasin_regrid.argtypes = [vp, C.c_int64, C.c_int64, C.c_int64, vp, vp, vp, C.c_uint32,
                                       vp, vp]
     lib.nmp_ldasin_downscale.argtypes = [vp, C.c_int64, C.c_int64, vp, C.c_double, vp, vp]
+    lib.nmp_ldasin_cosz.argtypes = [vp, C.c_int64, C.c_int64, vp, C.c_double, C.c_double,
+                                    C.c_double, vp, vp]
+    lib.nmp_forcing_from_ldasin_interp.argtypes = [vp, C.c_int64, C.c_int64, vp, vp, C.c_double,
+                                                   C.c_uint32, C.c_int, C.c_double, vp, C.c_double,
+                                                   C.c_double, C.c_double, vp, vp]
     lib.nmp_ldasout_grid.argtypes = [vp, C.c_int64, C.c_int64, C.c_int64, C.c_int, vp, vp,
                                      C.c_double, vp, vp]
     lib.nmp_accumulate.argtypes = [vp, C.c_int64, C.c_int64, C.c_float, vp, vp, vp, vp]
@@ -146,6 +151,7 @@ def load(build_if_missing: bool = False):
 EXPORTED_SYMBOLS = ["nmp_read_tables", "nmp_init", "nmp_step", "nmp_step_binned", "nmp_rebin", "nmp_forcing_synth", "nmp_forcing_from_ldasin", "nmp_forcing_from_ldasin_geo", "nmp_ldasin_ingest", "nmp_ldasout_grid",
                     "nmp_accumulate", "nmp_water_storage", "nmp_accum_finish",
                     "nmp_region_reduce", "nmp_ldasin_regrid", "nmp_ldasin_downscale",
+                    "nmp_ldasin_cosz", "nmp_forcing_from_ldasin_interp",
                     "nmp_run", "nmp_run_out", "nmp_frh2o", "nmp_frh2o_host", "nmp_calhum",
                     "nmp_calhum_host",
                     "nmp_state_from_aos", "nmp_sflx_columns", "nmp_sflx_column",

@@ -7,6 +7,8 @@
                               [--regions-only]]
                              [--forcing-grid FILE [--downscale] [--lapse-rate K_PER_M]
                               [--nearest RAINRATE,SWDOWN]]
+                             [--interp [--interp-hold VAR[,VAR]]
+                              [--interp-sw zenith|linear|hold] [--cosz-floor X]]
 
 Reads the namelist like the reference (noahmp_amd.config.Config ==
 offline/noahmp_config.Config) and then does what the reference driver does
@@ -80,6 +82,19 @@ def main(argv=None):
     ap.add_argument("--nearest", default="", metavar="VAR[,VAR]",
                     help="with --forcing-grid: LDASIN variables that take their nearest source "
                          "point instead of the bilinear value, e.g. RAINRATE,SWDOWN")
+    ap.add_argument("--interp", action="store_true",
+                    help="netCDF cases: interpolate the forcing between input times on the "
+                         "device (nmp_forcing_from_ldasin_interp) instead of holding each file's "
+                         "values over its input interval")
+    ap.add_argument("--interp-hold", default="RAINRATE", metavar="VAR[,VAR]",
+                    help="with --interp: LDASIN variables held at the earlier file's value "
+                         "(default RAINRATE, an interval rate)")
+    ap.add_argument("--interp-sw", default="zenith", choices=("zenith", "linear", "hold"),
+                    help="with --interp: SWDOWN follows the step's own COSZ through the files' "
+                         "clearness ratios (default), or is interpolated linearly, or held")
+    ap.add_argument("--cosz-floor", type=float, default=0.05, metavar="X",
+                    help="with --interp-sw zenith: lower bound of COSZ in the clearness ratio "
+                         "SWDOWN / max(COSZ, X) (default 0.05)")
     a = ap.parse_args(argv)
     if a.regions_only and not a.regions:
         ap.error("--regions-only needs --regions")
@@ -96,15 +111,21 @@ def main(argv=None):
             rkw.update(forcing_grid=a.forcing_grid, downscale=a.downscale,
                        lapse_rate=a.lapse_rate,
                        nearest=tuple(v for v in a.nearest.split(",") if v))
-        drv = driver.OfflineDriver.from_files(cfg, device=a.device, params=P, init=a.restart,
+        if a.interp:
+            hold = [v for v in a.interp_hold.split(",") if v]
+            if a.interp_sw == "hold" and "SWDOWN" not in hold:
+                hold.append("SWDOWN")
+            rkw.update(interp=True, hold=tuple(hold), sw_zenith=a.interp_sw == "zenith",
+                       cosz_floor=a.cosz_floor)
+        drv =driver.OfflineDriver.from_files(cfg, device=a.device, params=P, init=a.restart,
                                               precision=a.precision, cosz=a.cosz,
                                               ingest=not a.no_ingest, accumulate=a.accumulate,
                                               **rkw)
         a.ncol = drv.cs.ncol
     else:
-        if a.regions or a.forcing_grid:
-            ap.error("--regions and --forcing-grid need a run from files (the namelist's "
-                     "static_parameter_file)")
+        if a.regions or a.forcing_grid or a.interp:
+            ap.error("--regions, --forcing-grid and --interp need a run from files (the "
+                     "namelist's static_parameter_file)")
         cols = cases.make_columns(a.ncol, a.kind, P.as_dict(), seed=0,
                                   julian=timeman.julian(cfg.begdatetime))
         drv = driver.OfflineDriver(cfg, cols, device=a.device, params=P,
@@ -119,6 +140,9 @@ def main(argv=None):
           f"{len(drv.written) + len(drv.regions_written)} output files in {cfg.outdir}; "
           "status bits set on "
           f"{int((drv.cs.status != 0).sum())} columns")
+    if drv.interp_held:
+        print("interp: no input file at the end of the interval of "
+              f"{', '.join(t.isoformat() for t in drv.interp_held)}; it ran held")
     return 0
 
 

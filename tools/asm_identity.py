@@ -73,6 +73,11 @@ def filtered_sha(path):
 def record(parent_dir, pr_dir):
     same = True
     for unit, _, flags in units():
+        if not os.path.exists(os.path.join(parent_dir, asm_name(unit))):
+            b, nb = filtered_sha(os.path.join(pr_dir, asm_name(unit)))
+            print(f"unit   {unit}\nflags  {' '.join(flags)}\nparent (no such unit)\n"
+                  f"pr     {b} ({nb} lines)\nNEW\n")
+            continue
         a, na = filtered_sha(os.path.join(parent_dir, asm_name(unit)))
         b, nb = filtered_sha(os.path.join(pr_dir, asm_name(unit)))
         same &= a == b

@@ -5,6 +5,14 @@ achieved HBM bandwidth against their algorithmic bytes, at 1,048,576 columns.
                            (48 B fp32 / 96 B fp64)
   forcing_from_ldasin_geo  reads 8 rows (32 B) + geo (24 B), writes 12 fields;
                            one double cosine per column
+  forcing_from_ldasin_interp  reads both blocks of the input interval (2 x 36 B
+                           with the zenith scheme, counted whole although a
+                           held row of block 1 is not loaded; 2 x 32 B for the
+                           linear case, which reads no COSZ row) + geo (24 B),
+                           writes 12 fields; one double cosine and, with the
+                           zenith scheme, two double divisions per column
+  ldasin_cosz              reads geo (24 B), writes one row (4 B); one double
+                           cosine per column, once per input file
   ldasin_ingest            reads 8 gathered 4-byte words + the point (36 B),
                            writes 8 rows (32 B)
   ldasin_regrid            reads 4 corners + 4 weights (48 B) and 32 gathered
@@ -62,6 +70,7 @@ def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--ncol", type=int, default=1 << 20)
     ap.add_argument("--reps", type=int, default=50)
+    ap.add_argument("--out", default=None, help="also write the results as one JSON list")
     a = ap.parse_args()
     n, dev = a.ncol, "cuda:0"
     rng = np.random.default_rng(0)
@@ -87,6 +96,9 @@ def main():
     dz = torch.as_tensor(rng.uniform(-500, 500, n).astype(np.float32), device=dev)
     blk2 = torch.as_tensor(rng.uniform(250, 300, (L.NLDASIN, n)).astype(np.float32), device=dev)
     near = nearest_mask(("RAINRATE", "SWDOWN"))
+    # the interval's other block, and the driver's default hold (RAINRATE)
+    blk_b = torch.as_tensor(rng.uniform(1, 2, (L.NLDASIN, n)).astype(np.float32), device=dev)
+    hold = 1 << L.LDASIN.index("RAINRATE")
     out = []
     for prec in (4, 8):
         eng = Engine(Params.builtin(), L.CASE_NML_OPTIONS, device=0, precision=prec)
@@ -101,7 +113,18 @@ def main():
             ("forcing_from_ldasin_geo", None, lambda: eng.forcing_from_ldasin(blk, f, geo=geo,
                                                                               solar=solar),
              n * (32 + 24 + 12 * prec)),
+            ("forcing_from_ldasin_interp", "zenith, RAINRATE held",
+             lambda: eng.forcing_from_ldasin_interp(blk, blk_b, 1 / 3, f, geo, solar, hold, True,
+                                                    0.05),
+             n * (2 * 36 + 24 + 12 * prec)),
+            ("forcing_from_ldasin_interp", "linear, none held",
+             lambda: eng.forcing_from_ldasin_interp(blk, blk_b, 1 / 3, f, geo, solar, 0, False,
+                                                    0.05),
+             n * (2 * 32 + 24 + 12 * prec)),
         ]
+        if prec == 4:
+            cases.append(("ldasin_cosz", None, lambda: eng.ldasin_cosz(blk_b, geo, solar),
+                          n * (24 + 4)))
         for order, pt in points.items():
             cases.append(("ldasout_grid", order,
                           lambda pt=pt: eng.ldasout_grid(diag, pt, grids, -9999.0),
@@ -127,6 +150,10 @@ def main():
             print(json.dumps(r), flush=True)
             out.append(r)
         eng.close()
+    if a.out:
+        os.makedirs(os.path.dirname(os.path.abspath(a.out)), exist_ok=True)
+        with open(a.out, "w") as fh:
+            json.dump(out, fh, indent=1)
     return 0
 
 

@@ -4,7 +4,7 @@ seeded synthetic generator on a regular lat-lon grid.  noahmp_offline.py then
 runs it from the files.
 
     python tools/make_offline_case.py case.nml [--ny 32 --nx 64 --kind conus]
-                                      [--forcing-grid SY SX]
+                                      [--forcing-grid SY SX] [--closing-file]
 
 --forcing-grid SY SX: the LDASIN files are written on a coarser SY x SX
 rectilinear grid that covers the model grid, with a forcing-grid file
@@ -36,6 +36,9 @@ def main(argv=None):
     ap.add_argument("--seed", type=int, default=0)
     ap.add_argument("--forcing-grid", type=int, nargs=2, default=None, metavar=("SY", "SX"),
                     help="write the LDASIN files on a coarser SY x SX grid, plus forcing_grid.nc")
+    ap.add_argument("--closing-file", action="store_true",
+                    help="also write the LDASIN file at enddatetime, which `noahmp_offline.py "
+                         "--interp` reads as the last input interval's other end")
     a = ap.parse_args(argv)
     cfg = config.Config(a.nmlfile)
     lat = a.lat0 + a.dlat * np.arange(a.ny)[:, None] + 0.0 * np.arange(a.nx)[None, :]
@@ -57,7 +60,8 @@ def main(argv=None):
     if a.forcing_grid:
         fcols, fgrid, where = _forcing_grid(a, cfg, lat, lon, P)
     every, t, k = cfg.input_interval, cfg.begdatetime, 0
-    while t < cfg.enddatetime:
+    # (--closing-file: also the last interval's other end, the file at enddatetime)
+    while t < cfg.enddatetime or (a.closing_file and t - every < cfg.enddatetime):
         f = cases.forcing_step(fcols, timeman.julian(t), timeman.yearlen(t.year), k, seed=a.seed)
         ncio.write_ldasin(ncio.ldasin_path(cfg.indir, t), fgrid, f, t, extras=False)
         t, k = t + every, k + 1

@@ -26,6 +26,10 @@ case with its LDASIN files on a coarse SY x SX source grid (e.g. 128 256),
 regridded on the device (nmp_ldasin_regrid), with and without the elevation
 downscaling, against the same values fed as pre-regridded model-grid files
 (nmp_ldasin_ingest) -- ms per step and bytes uploaded per input interval.
+
+--interp-runs N times interpolation between input times instead: the same case
+with 3-hourly files, N fresh runs each with interp=True and without (the held
+path), interleaved -- ms per step of every run, median and range per variant.
 """
 import argparse
 import json
@@ -58,7 +62,8 @@ def write_namelist(d: str) -> str:
 UPLOAD_LABEL = {"host": "12 fields", "device-synth": "12 fields", "ldasin-step": "ldasin block",
                 "ldasin-block": "ldasin block + device cosz",
                 "ldasin-ingest": "file bytes, device ingest + cosz",
-                "ldasin-regrid": "coarse file bytes, device regrid"}
+                "ldasin-regrid": "coarse file bytes, device regrid",
+                "ldasin-interp": "file bytes, device ingest + interpolation in time"}
 
 
 def time_driver(cfg, precision, ldasin, warm, steps, threads, cosz="host", ingest=False, **kw):
@@ -161,8 +166,43 @@ def coarse_forcing_runs(a, nml):
     return runs
 
 
+def interp_runs(a, nml):
+    """The case with 3-hourly files (and the closing one): fresh runs with
+    interp (resident blocks of both ends, nmp_forcing_from_ldasin_interp every
+    step) and without (today's held path), interleaved; ms per step of each
+    run, and each variant's median and range."""
+    import make_offline_case
+    text = open(nml).read().replace("input_frequency = '1 hour'", "input_frequency = '3 hour'")
+    with open(nml, "w") as f:
+        f.write(text)
+    make_offline_case.main([nml, "--ny", str(a.ny), "--nx", str(a.nx), "--kind", "mixed",
+                            "--closing-file"])
+    cfg = config.Config(nml)
+    runs = {"held": [], "interp": []}
+    for i in range(a.interp_runs):
+        for name, kw in (("held", {}), ("interp", dict(interp=True))):
+            r, _, drv = time_driver(cfg, 4, True, a.warm, a.steps, a.threads, "device", True, **kw)
+            r["variant"], r["round"] = name, i
+            print(json.dumps(r), flush=True)
+            runs[name].append(r)
+            del drv
+    summary = {}
+    for name, rs in runs.items():
+        ms = sorted(r["ms_per_step"] for r in rs)
+        summary[name] = {"runs": len(ms), "median_ms_per_step": float(np.median(ms)),
+                         "min_ms_per_step": ms[0], "max_ms_per_step": ms[-1]}
+    print(json.dumps(summary), flush=True)
+    return {"case": f"{a.ny} x {a.nx} land points (mixed USGS/STAS columns), 900-s steps, "
+                    "3-hourly LDASIN with the closing file, 3-hourly LDASOUT; fp32, file bytes "
+                    "ingested on the device; fresh drivers, variants interleaved",
+            "summary": summary, "driver": runs["held"] + runs["interp"]}
+
+
 def main():
     ap = argparse.ArgumentParser()
+    ap.add_argument("--interp-runs", type=int, default=0, metavar="N",
+                    help="time N fresh runs each with and without interp on 3-hourly files, "
+                         "interleaved, instead")
     ap.add_argument("--forcing-grid", type=int, nargs=2, default=None, metavar=("SY", "SX"),
                     help="time the coarse-forcing path against pre-regridded files instead")
     ap.add_argument("--ny", type=int, default=1024)
@@ -176,6 +216,13 @@ def main():
     a = ap.parse_args()
     os.makedirs(a.dir, exist_ok=True)
     nml = write_namelist(a.dir)
+    if a.interp_runs:
+        res = interp_runs(a, nml)
+        if a.out:
+            os.makedirs(os.path.dirname(os.path.abspath(a.out)), exist_ok=True)
+            with open(a.out, "w") as f:
+                json.dump(res, f, indent=1)
+        return 0
     if a.forcing_grid:
         runs = coarse_forcing_runs(a, nml)
         if a.out:
