@@ -509,6 +509,22 @@ int nmp_region_reduce(nmp_engine* eng, int64_t ncol, int64_t ld, int nfield, con
              : NMP_E_DEVICE;
 }
 
+int nmp_state_output(nmp_engine* eng, int64_t ncol, int64_t ld, const void* state,
+                     const int32_t* isnow, const int32_t* static_i, uint32_t groups,
+                     double fill, void* out, int64_t ld_out, void* stream) {
+  if (!eng || ncol < 0 || ld < ncol || ld >= kMaxColumns || ld_out < ncol ||
+      ld_out >= kMaxColumns || groups == 0 || (groups >> NMP_NXGROUP) != 0)
+    return NMP_E_ARG;
+  if (ncol == 0) return NMP_OK;
+  if (!state || !isnow || !static_i || !out) return NMP_E_ARG;
+  if (ensure_device(eng->device) != NMP_OK) return NMP_E_DEVICE;
+  return nmp::launch_state_output(eng->precision, eng->dparams, ncol, ld, state, isnow, static_i,
+                                  groups, fill, out, ld_out,
+                                  static_cast<hipStream_t>(stream)) == hipSuccess
+             ? NMP_OK
+             : NMP_E_DEVICE;
+}
+
 int nmp_forcing_from_ldasin_geo(nmp_engine* eng, int64_t ncol, int64_t ld, const float* ldasin,
                                 const double* geo, double sin_decl, double cos_decl, double ha0,
                                 void* forcing, void* stream) {

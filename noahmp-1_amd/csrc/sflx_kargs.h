@@ -100,6 +100,13 @@ hipError_t launch_region_reduce(int precision, int64_t ncol, int64_t ld, int nfi
                                 const double* wsum, double* partial, double* sums, double* means,
                                 hipStream_t stream);
 
+// csrc/stateout.hip: the selected NMP_X_* groups of the state block as compact
+// output rows (the two per-type table values come from P)
+hipError_t launch_state_output(int precision, const DevParams* P, int64_t ncol, int64_t ld,
+                               const void* state, const int32_t* isnow, const int32_t* static_i,
+                               uint32_t groups, double fill, void* out, int64_t ld_out,
+                               hipStream_t stream);
+
 // csrc/routines.hip: the reference's public routines frh2o / calhum over n
 // elements (device pointers, engine precision; math 0 = the fp32 "ref" policy)
 hipError_t launch_frh2o(int precision, int math, const DevParams* P, int64_t n,

@@ -18,6 +18,9 @@ offline/noahmp_config.py has no time loop, forcing reader or writer, SURVEY
   with ``accumulate=True`` each file also carries the interval's accumulated
   output (layout.BUDGET: means, totals and the water budget's closure, added up
   on the device after every step: nmp_accumulate / nmp_accum_finish);
+  with ``state_out`` each file also carries the selected groups of the land
+  state -- soil, snow and canopy fields (layout.STATE_OUT), formed on the
+  device from the state the output step left (nmp_state_output);
   with ``regions`` each output step also writes the regions' weighted means of
   every output field as ``<YYYYMMDDHH>.REGIONS_DOMAIN1`` (nmp_region_reduce on
   the output block, on rank 0; ``write_grids=False`` then drops the grids);
@@ -53,7 +56,7 @@ import numpy as np
 import torch
 import torch.distributed as dist
 
-from . import cases, layout as L, ncio, shard, timeman
+from . import cases, layout as L, ncio, shard, stateout, timeman
 from .config import Config
 from .engine import ColumnState, Engine, StreamShards
 from .feeds import (DeviceSyntheticForcing, ForcingUpload, HostFeed,  # noqa: F401  (re-exported)
@@ -127,7 +130,7 @@ class OfflineDriver:
                  regions=None, region_weights="area", write_grids: bool = True,
                  downscale: bool = False, lapse_rate: float = 0.0065, interp: bool = False,
                  hold=("RAINRATE",), sw_zenith: bool = True, cosz_floor: float = 0.05,
-                 prefetch: bool = True):
+                 prefetch: bool = True, state_out=None):
         """cols: this rank's columns (all of them on a single rank); under an
         initialised process group they must be the rank's shard_range block of
         the global column set.  ldasin_upload: with a provider that has
@@ -177,7 +180,22 @@ class OfflineDriver:
         instead of reading ahead.  Refused with cosz="host",
         ldasin_upload=False, a provider without files or device-synthetic
         forcing.  Off (the default), every code path and output byte is as
-        without it."""
+        without it.
+        state_out: "all", a comma-separated string or an iterable of
+        state-output group names (layout.STATE_OUT: soil moisture and
+        temperature, the snow pack, canopy water, LAI, the water table, the
+        water storage, the carbon pools, ...).  Output steps then also form
+        those groups' rows from the state on each range's stream right after
+        the step (nmp_state_output; after nmp_accum_finish when accumulating)
+        and write them after the fluxes, a layered group as one variable over
+        a layer dimension.  REGIONS files carry the fluxes and the groups that
+        cannot hold the fill value.  Refused in a run that writes no output.
+        None (the default): every code path and output byte is as without it."""
+        self.state_mask = 0
+        if state_out is not None:
+            self.state_mask = stateout.parse_groups(state_out)
+            if not write or cfg.output_interval is None:
+                raise ValueError("state_out needs a run that writes output")
         if not write_grids and regions is None:
             raise ValueError("write_grids=False needs regions: the run would write nothing")
         # (a bad cosz, downscale or interp is refused before any device work)
@@ -210,16 +228,23 @@ class OfflineDriver:
         self.t, self.step_index, self.write = cfg.begdatetime, 0, write
         self.accumulate = bool(accumulate)
         self.out_names = L.DIAG_OUT_ACC if self.accumulate else L.DIAG_OUT
+        self.nflux, region_rows = len(self.out_names), None
+        if self.state_mask:
+            # the block's rows: the fluxes, then the selected state rows, the
+            # groups that can hold the fill value last; the regions stop before them
+            self.out_names = list(self.out_names) + stateout.row_names(self.state_mask)
+            region_rows = self.nflux + stateout.nofill_rows(self.state_mask)
         nout = len(self.out_names)
         self.diag = torch.zeros((nout, self.cs.ncol), dtype=self.dtype, device=self.dev)
         self.accum = None
         if self.accumulate:
             self.accum = Accumulation(self.engine, self.cs, self.dt)
-            if grid is not None:
-                # a grid whose 35 fields pass the classic format's offsets fails
-                # here, not on a writer thread after the first interval
-                ncio.ldasout_header(grid, "f4" if self.dtype == torch.float32 else "f8",
-                                    cfg.begdatetime, self.out_names)
+        if (self.accumulate or self.state_mask) and grid is not None:
+            # a grid whose 35 fields or state rows do not pass the classic
+            # format's offsets fails here, not on a writer thread after the
+            # first interval
+            ncio.ldasout_header(grid, "f4" if self.dtype == torch.float32 else "f8",
+                                cfg.begdatetime, self.out_names)
         # the 12-field host form, which every run has, and the run's own path
         host = HostFeed(self.forcing, self.cs.ncol, self.dtype, self.dev, bool(downscale))
         feed = self.feed = make_feed(kind, host, self.engine, self.cs.ncol, self.dtype, self.dev,
@@ -248,7 +273,7 @@ class OfflineDriver:
         # the output staging buffers up front, out of the time loop (OutputWriter)
         self.output = OutputWriter(self.engine, cfg, grid, self.out_names, total, self.dtype,
                                    self.dev, write and cfg.output_interval is not None and rank0,
-                                   self.region_plan, self.write_grids)
+                                   self.region_plan, self.write_grids, region_rows=region_rows)
         self.written, self.regions_written = self.output.written, self.output.regions_written
         self.n_out = 0
 
@@ -422,9 +447,13 @@ class OfflineDriver:
             dstep, level, post = None, L.DIAG_NONE, None
             if out:
                 dstep, level = diag, L.DIAG_OUT_LEVEL
+                if self.state_mask:
+                    dstep = diag[:L.NDIAG_OUT]
             if self.accum is not None:  # every step writes its fluxes
                 level = L.DIAG_OUT_LEVEL
                 dstep, post = self.accum.step(f, diag, out)
+            if out and self.state_mask:
+                post = self._state_post(diag[self.nflux:], post)
             self.ranges.step(f, self.zsoil, self.dt, timeman.julian(t0), timeman.yearlen(t0.year),
                              dstep, level, after=after, pre=pre, post=post)
             self.feed.launched(t0, self.ranges.producers)
@@ -444,6 +473,17 @@ class OfflineDriver:
         torch.cuda.synchronize(self.dev)
         self.flush_output()
         return self
+
+    def _state_post(self, rows: torch.Tensor, first):
+        """StreamShards.step's `post` of an output step with state output:
+        `first` (the accumulation's, or None), then the range's columns of the
+        state rows -- the block's trailing rows -- from the state the step left."""
+        def post(st, rng):
+            if first is not None:
+                first(st, rng)
+            self.engine.state_output(self.cs, self.state_mask, rows, float(ncio.FILL), stream=st,
+                                     cols=rng)
+        return post
 
     def _output_step(self, t1: datetime.datetime, b, rank: int):
         """Hand the output step's block to the writer: the gathered one

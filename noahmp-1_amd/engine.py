@@ -438,6 +438,29 @@ class Engine:
                                               _ptr(out, lo), C.c_void_p(s.cuda_stream)),
                    "nmp_accum_finish")
 
+    # ---- state output (nmp_state_output) ---------------------------------------
+    def state_output(self, cs: ColumnState, groups: int, out_rows: torch.Tensor, fill: float,
+                     stream=None, cols: tuple[int, int] | None = None):
+        """nmp_state_output: the rows of the state-output groups in the mask
+        `groups` (stateout.parse_groups; layout.STATE_OUT) of every column into
+        out_rows (len(stateout.rows(groups)), n), engine precision, `fill` on
+        inactive snow layers; stateout.state_output_host is the numpy form.
+        out_rows may be a block's trailing rows (a contiguous row slice).
+        cols=(lo, hi) writes only those columns, enqueued on `stream`."""
+        from . import stateout
+        n = cs.ncol
+        lo, hi = self._cols_range(n, cols)
+        nrow = len(stateout.rows(groups))   # ValueError for an empty or out-of-range mask
+        self._check_block(cs.state, (L.NSTATE, n), self.dtype, "state")
+        self._check_block(cs.isnow, (n,), torch.int32, "isnow")
+        self._check_block(cs.static_i, (L.NSTATIC_I, n), torch.int32, "static_i")
+        self._check_block(out_rows, (nrow, n), self.dtype, "out_rows")
+        s = stream if stream is not None else torch.cuda.current_stream(self.device)
+        _lib.check(self._lib.nmp_state_output(self._h, hi - lo, n, _ptr(cs.state, lo),
+                                              _ptr(cs.isnow, lo), _ptr(cs.static_i, lo),
+                                              int(groups), float(fill), _ptr(out_rows, lo), n,
+                                              C.c_void_p(s.cuda_stream)), "nmp_state_output")
+
     # ---- region-aggregated output (nmp_region_reduce) ---------------------------
     def region_reduce(self, fields: torch.Tensor, plan, sums: torch.Tensor,
                       means: torch.Tensor | None = None, stream=None):

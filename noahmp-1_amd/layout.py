@@ -50,6 +50,22 @@ assert NACC == 17 and NBUDGET == 19
 # the LDASOUT fields of an accumulating run: the output step's fluxes, then the interval's
 DIAG_OUT_ACC = DIAG_OUT + BUDGET
 
+# state output groups (NMP_X_*, nmp_state_output): (name, rows, can hold the
+# fill value); the groups that cannot come first
+STATE_OUT = [
+    ("SOIL_M", 4, False), ("SOIL_W", 4, False), ("SOIL_T", 4, False), ("SNEQV", 1, False),
+    ("SNOWH", 1, False), ("TG", 1, False), ("TV", 1, False), ("LAI", 1, False), ("SAI", 1, False),
+    ("ZWT", 1, False), ("WA", 1, False), ("CANWAT", 1, False), ("ISNOW", 1, False),
+    ("SNOWLIQ", 1, False), ("TWS", 1, False), ("SOILSAT", 1, False), ("ROOT_M", 1, False),
+    ("CARBON", 6, False), ("SNOW_T", 3, True), ("SNOW_Z", 3, True), ("SNOWT_AVG", 1, True),
+]
+NXGROUP = len(STATE_OUT)
+NXROWS_NOFILL = sum(w for _, w, f in STATE_OUT if not f)
+NXROWS = sum(w for _, w, _ in STATE_OUT)
+assert NXGROUP == 21 and NXROWS_NOFILL == 32 and NXROWS == 39
+# the six 2-D variables of the CARBON group, in row order
+CARBON_POOLS = ["LFMASS", "RTMASS", "STMASS", "WOOD", "STBLCP", "FASTCP"]
+
 # status bits (NMP_ST_*)
 ST_ERRSW, ST_ERRENG, ST_FIRE, ST_HCAN, ST_ZLVL, ST_FLERCH, ST_OPTVEG, ST_STOP = (
     1, 2, 4, 8, 16, 32, 64, 128)

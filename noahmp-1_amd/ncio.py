@@ -26,7 +26,10 @@ scipy.io.netcdf_file (no netCDF-4/HDF5 library exists in this image):
   output fluxes on the grid, _FillValue off the land mask; an accumulating run
   (driver accumulate=True) appends its interval's 19 fields (layout.BUDGET) and
   stores the interval so far in its restart files (write_state accum,
-  read_accum);
+  read_accum); a run with state output (driver state_out) appends the selected
+  groups of the land state (layout.STATE_OUT), a layered group as one variable
+  over (Time, soil_layers_stag | snow_layers, south_north, west_east),
+  layer-major;
 * REGIONS, one file per output time of a run with regions,
   ``<YYYYMMDDHH>.REGIONS_DOMAIN1``: dimension `region`, region_id, ncolumns,
   weight and one double variable per output field holding the regions'
@@ -698,13 +701,39 @@ def write_ldasout(path: str, grid: Grid, diag: np.ndarray, t: datetime.datetime,
         f.createDimension("south_north", ny)
         f.createDimension("west_east", nx)
         f.valid_time = t.isoformat()
-        dims = ("Time", "south_north", "west_east")
-        for i, name in enumerate(names):
-            v = f.createVariable(name, kind, dims)
-            v._FillValue = np.asarray(FILL, kind)
-            v[0] = full[i].reshape(ny, nx)
+        variables = _ldasout_variables(names)
+        for d, w in _layer_dims(variables):
+            f.createDimension(d, w)
+        for name, i, w, ldim in variables:
+            if ldim is None:
+                v = f.createVariable(name, kind, ("Time", "south_north", "west_east"))
+                v._FillValue = np.asarray(FILL, kind)
+                v[0] = full[i].reshape(ny, nx)
+            else:  # layer-major: the group's consecutive grids are the variable's bytes
+                v = f.createVariable(name, kind, ("Time", ldim, "south_north", "west_east"))
+                v._FillValue = np.asarray(FILL, kind)
+                v[0] = full[i:i + w].reshape(w, ny, nx)
     finally:
         f.close()
+
+
+def _ldasout_variables(names):
+    """(variable, first row, rows, layer dimension or None) of an output
+    block's row names: the rows NAME_1..NAME_w of a layered state-output group
+    (stateout.row_names) are one variable over a layer dimension."""
+    from .stateout import variables
+    return variables(names)
+
+
+def _layer_dims(variables):
+    """(dimension, length) of the layer dimensions the variables use, in order
+    of first use."""
+    from .stateout import LAYER_DIMS
+    out = []
+    for _, _, _, ldim in variables:
+        if ldim is not None and ldim not in [d for d, _ in out]:
+            out.append((ldim, LAYER_DIMS[ldim]))
+    return out
 
 
 def _nc_name(s: str) -> bytes:
@@ -717,31 +746,42 @@ def ldasout_header(grid: Grid, kind: str, t: datetime.datetime, names=L.DIAG_OUT
     16 flux variables, or of `names`, over (Time, south_north, west_east), the
     valid_time global attribute, each variable's _FillValue), built from the format's
     layout: magic, numrecs, dimension / attribute / variable lists, each
-    variable's type, per-record size and data offset."""
+    variable's type, per-record size and data offset.  The rows NAME_1..NAME_w
+    of a layered state-output group are one variable over a layer dimension
+    (soil_layers_stag, snow_layers), declared only when such a group is
+    present; without one the bytes are what they were."""
     ny, nx = grid.shape
     i4 = lambda v: np.array(v, ">i4").tobytes()  # noqa: E731
     item = np.dtype(kind).itemsize
     nc_type = {4: 5, 8: 6}[item]                 # NC_FLOAT, NC_DOUBLE
     fill = np.asarray(FILL, np.dtype(kind).newbyteorder(">")).tobytes()
-    h = [b"CDF\x01", i4(1), i4(10), i4(3)]       # NC_DIMENSION, 3 dims
-    for name, n in (("Time", 0), ("south_north", ny), ("west_east", nx)):
+    variables = _ldasout_variables(names)
+    ldims = _layer_dims(variables)                # only with a layered state-output group
+    h = [b"CDF\x01", i4(1), i4(10), i4(3 + len(ldims))]  # NC_DIMENSION
+    for name, n in (("Time", 0), ("south_north", ny), ("west_east", nx), *ldims):
         h += [_nc_name(name), i4(n)]
+    dimid = {d: 3 + k for k, (d, _) in enumerate(ldims)}
     vt = t.isoformat().encode("latin1")
     h += [i4(12), i4(1), _nc_name("valid_time"), i4(2), i4(len(vt)), vt,
           b"\x00" * (-len(vt) % 4)]               # NC_ATTRIBUTE, NC_CHAR
-    h += [i4(11), i4(len(names))]                # NC_VARIABLE
-    vsize = ny * nx * item
-    vsize += -vsize % 4
-    metas = []
-    for name in names:
-        metas.append([_nc_name(name), i4(3), i4(0), i4(1), i4(2), i4(12), i4(1),
+    h += [i4(11), i4(len(variables))]            # NC_VARIABLE
+    metas, vsizes = [], []
+    for name, _, w, ldim in variables:
+        vsize = w * ny * nx * item
+        vsize += -vsize % 4
+        shape = [i4(3), i4(0), i4(1), i4(2)] if ldim is None else \
+            [i4(4), i4(0), i4(dimid[ldim]), i4(1), i4(2)]
+        metas.append([_nc_name(name), *shape, i4(12), i4(1),
                       _nc_name("_FillValue"), i4(nc_type), i4(1), fill, i4(nc_type), i4(vsize)])
+        vsizes.append(vsize)
     size = sum(len(x) for x in h) + sum(sum(len(x) for x in m) + 4 for m in metas)
-    if size + len(metas) * vsize > 2**31 - 1:  # CDF-1 offsets are signed 32-bit
+    if size + sum(vsizes) > 2**31 - 1:  # CDF-1 offsets are signed 32-bit
         raise ValueError(f"LDASOUT of {len(names)} {ny} x {nx} {kind} grids exceeds the classic "
                          "format's 2 GiB offsets")
-    for i, m in enumerate(metas):
-        h += m + [i4(size + i * vsize)]         # begin (32-bit offsets, version 1)
+    begin = size
+    for m, vsize in zip(metas, vsizes):
+        h += m + [i4(begin)]                     # begin (32-bit offsets, version 1)
+        begin += vsize
     return b"".join(h)
 
 
@@ -760,8 +800,14 @@ def write_ldasout_grids(path: str, grid: Grid, grids_be: np.ndarray, t: datetime
 
 
 def read_ldasout(path: str, grid: Grid, names=L.DIAG_OUT) -> np.ndarray:
+    """The rows `names` of an LDASOUT file as columns; NAME_<k> is layer k
+    (from 1) of a layered state-output variable NAME."""
     raw = read_ldasin(path)
-    return np.stack([grid.columns(raw[name]) for name in names])
+    rows = {}
+    for name, i, w, ldim in _ldasout_variables(names):
+        for k in range(w):
+            rows[i + k] = grid.columns(raw[name] if ldim is None else raw[name][k])
+    return np.stack([rows[i] for i in range(len(names))])
 
 
 # ---- REGIONS (region-aggregated output) ------------------------------------------

@@ -29,11 +29,16 @@ class OutputWriter:
     OUT_WRITERS, OUT_BUFFERS = 2, 3
 
     def __init__(self, engine, cfg, grid, out_names, ncol_total: int, dtype, dev, stage: bool,
-                 region_plan=None, write_grids: bool = True, perm=None):
+                 region_plan=None, write_grids: bool = True, perm=None,
+                 region_rows: int | None = None):
+        """region_rows: the block's leading rows the regions reduce (default:
+        all of them); a run with state output leaves out its trailing rows,
+        which can hold the fill value."""
         self.engine, self.cfg, self.grid, self.out_names = engine, cfg, grid, out_names
         self.dev, self.region_plan, self.write_grids, self.perm = dev, region_plan, write_grids, perm
         self.written, self.regions_written = [], []
         nout = len(out_names)
+        self.region_rows = nout if region_rows is None else int(region_rows)
         self._writer = ThreadPoolExecutor(self.OUT_WRITERS)
         self._out_host = [None] * self.OUT_BUFFERS
         if stage and write_grids:
@@ -49,9 +54,10 @@ class OutputWriter:
         self._reg_dev, self._reg_host = None, [None] * self.OUT_BUFFERS
         if region_plan is not None:
             # sums and means of an output step, and their pinned staging buffers
-            self._reg_dev = torch.zeros((2, nout, region_plan.nreg), dtype=torch.float64,
-                                        device=dev)
-            self._reg_host = [torch.empty((2, nout, region_plan.nreg), dtype=torch.float64,
+            self._reg_dev = torch.zeros((2, self.region_rows, region_plan.nreg),
+                                        dtype=torch.float64, device=dev)
+            self._reg_host = [torch.empty((2, self.region_rows, region_plan.nreg),
+                                          dtype=torch.float64,
                                           pin_memory=True) for _ in range(self.OUT_BUFFERS)]
 
     def _grids(self, d: torch.Tensor, stream) -> torch.Tensor:
@@ -64,8 +70,11 @@ class OutputWriter:
             self._out_dev = torch.empty((d.shape[0], npts), device=self.dev,
                                         dtype=torch.int32 if d.dtype == torch.float32
                                         else torch.int64)
-        self.engine.ldasout_grid(d, self._out_point, self._out_dev, float(ncio.FILL),
-                                 stream=stream)
+        # (nmp_ldasout_grid takes at most NDIAG_FULL rows a call)
+        for r in range(0, d.shape[0], L.NDIAG_FULL):
+            self.engine.ldasout_grid(d[r:r + L.NDIAG_FULL], self._out_point,
+                                     self._out_dev[r:r + L.NDIAG_FULL], float(ncio.FILL),
+                                     stream=stream)
         return self._out_dev
 
     def write(self, d: torch.Tensor, path: str, t1: datetime.datetime, stream):
@@ -93,8 +102,8 @@ class OutputWriter:
         h, rh, rpath = self._out_host[k], None, None
         if self.region_plan is not None:
             rh, rpath = self._reg_host[k], ncio.regions_path(self.cfg.outdir, t1)
-            self.engine.region_reduce(d, self.region_plan, self._reg_dev[0], self._reg_dev[1],
-                                      stream=stream)
+            self.engine.region_reduce(d[:self.region_rows], self.region_plan, self._reg_dev[0],
+                                      self._reg_dev[1], stream=stream)
             self.regions_written.append(rpath)
         with torch.cuda.stream(stream):
             if src is not None:
@@ -113,7 +122,7 @@ class OutputWriter:
         if rh is not None:
             plan = self.region_plan
             ncio.write_regions(rpath, plan.region_id, plan.ncolumns, plan.wsum, rh.numpy()[1], t1,
-                               self.out_names)
+                               self.out_names[:self.region_rows])
         if h is None:
             return
         a = h.numpy()
@@ -179,7 +188,8 @@ class Accumulation:
         `diag`, the others' into the scratch block."""
         fluxes = diag[:L.NDIAG_OUT] if out else self.acc_diag
         self.steps += 1
-        post = self.post(fluxes, f, diag[L.NDIAG_OUT:] if out else None, self.steps * self.dt)
+        post = self.post(fluxes, f, diag[L.NDIAG_OUT:L.NDIAG_OUT + L.NBUDGET] if out else None,
+                         self.steps * self.dt)
         if out:
             self.steps = 0
         return fluxes, post

@@ -3,6 +3,7 @@
 
     python noahmp_offline.py [case.nml] [--ncol N] [--kind casenml|mixed|conus]
                              [--device D] [--restart FILE] [--accumulate]
+                             [--state-out all|NAME[,NAME...]]
                              [--regions FILE [--region-weights area|equal]
                               [--regions-only]]
                              [--forcing-grid FILE [--downscale] [--lapse-rate K_PER_M]
@@ -61,6 +62,11 @@ def main(argv=None):
                          "of the energy fluxes, totals of the water fluxes (ACCPRCP, ACCECAN, "
                          "..., SFCRNOFF, UGDRNOFF) and the water budget's closure (DSTOR, "
                          "WBRES) -- 35 fields per LDASOUT file instead of 16")
+    ap.add_argument("--state-out", default=None, metavar="all|NAME[,NAME...]",
+                    help="also write the land state at every output time: the named groups of "
+                         "soil, snow and canopy fields (SOIL_M, SOIL_W, SOIL_T, SNEQV, SNOWH, TG, "
+                         "TV, LAI, SAI, ZWT, WA, CANWAT, ISNOW, SNOWLIQ, TWS, SOILSAT, ROOT_M, "
+                         "CARBON, SNOW_T, SNOW_Z, SNOWT_AVG), or all of them")
     ap.add_argument("--regions", default=None, metavar="FILE",
                     help="netCDF cases: a region file on the run's grid (int REGION, optional "
                          "double AREA); every output time then also writes the regions' "
@@ -102,10 +108,18 @@ def main(argv=None):
         ap.error("--downscale and --nearest need --forcing-grid")
     cfg = config.Config(a.nmlfile)
     P = Params.builtin()
+    skw = {}
+    if a.state_out is not None:
+        from noahmp_amd import stateout
+        try:
+            stateout.parse_groups(a.state_out)
+        except ValueError as e:
+            ap.error(str(e))
+        skw = dict(state_out=a.state_out)
     if os.path.isfile(cfg.constfile):
-        rkw = {}
+        rkw = dict(skw)
         if a.regions:
-            rkw = dict(regions=a.regions, region_weights=a.region_weights,
+            rkw.update(regions=a.regions, region_weights=a.region_weights,
                        write_grids=not a.regions_only)
         if a.forcing_grid:
             rkw.update(forcing_grid=a.forcing_grid, downscale=a.downscale,
@@ -130,7 +144,7 @@ def main(argv=None):
                                   julian=timeman.julian(cfg.begdatetime))
         drv = driver.OfflineDriver(cfg, cols, device=a.device, params=P,
                                    forcing="device" if a.device_forcing else None,
-                                   precision=a.precision, accumulate=a.accumulate)
+                                   precision=a.precision, accumulate=a.accumulate, **skw)
         if a.restart:
             drv.load_restart(a.restart)
     t0 = time.perf_counter()

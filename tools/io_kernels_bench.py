@@ -23,6 +23,10 @@ achieved HBM bandwidth against their algorithmic bytes, at 1,048,576 columns.
                            double exponentials and five double divisions
   ldasout_grid             fills 16 grids (64 B per grid point), then reads 16
                            fluxes + the point (68 B) and scatters them (64 B)
+  state_output             every group: reads 44 state rows, ISNOW and 3 static
+                           rows (192 B fp32), writes 39 rows (156 B); SOIL_M
+                           alone: reads 4 rows, writes 4
+                           (stateout.algorithmic_bytes)
 
 The two gather/scatter kernels are timed with the grid points in the
 columns' own order (`point` = identity: coalesced) and fully shuffled (every
@@ -46,8 +50,8 @@ import numpy as np  # noqa: E402
 import torch  # noqa: E402
 
 import noahmp_pkg  # noqa: E402,F401
-from noahmp_amd import layout as L, timeman  # noqa: E402
-from noahmp_amd.engine import Engine  # noqa: E402
+from noahmp_amd import cases as cases_mod, layout as L, stateout, timeman  # noqa: E402
+from noahmp_amd.engine import ColumnState, Engine  # noqa: E402
 from noahmp_amd.params import Params  # noqa: E402
 
 PEAK_GBS = 8000.0  # MI355X HBM3E (/opt/skills/guides/MI355X_MICROARCH.md)
@@ -99,6 +103,11 @@ def main():
     # the interval's other block, and the driver's default hold (RAINRATE)
     blk_b = torch.as_tensor(rng.uniform(1, 2, (L.NLDASIN, n)).astype(np.float32), device=dev)
     hold = 1 << L.LDASIN.index("RAINRATE")
+    # state output: a mixed column set (every ISNOW, soil and lake, all types)
+    P = Params.builtin()
+    so_cols = cases_mod.make_columns(n, "mixed", P.as_dict(), seed=0)
+    so_cs = {4: ColumnState.from_host(so_cols, dev, torch.float32),
+             8: ColumnState.from_host(so_cols, dev, torch.float64)}
     out = []
     for prec in (4, 8):
         eng = Engine(Params.builtin(), L.CASE_NML_OPTIONS, device=0, precision=prec)
@@ -141,6 +150,16 @@ def main():
                       # (in place: repeated launches drift the block's values; timing only)
                       ("ldasin_downscale", None,
                        lambda: eng.ldasin_downscale(blk2, dz, 0.0065), n * (20 + 16))]
+        # state output: every group (44 state rows, ISNOW and 3 static rows
+        # read, 39 rows written) and SOIL_M alone (4 rows read, 4 written)
+        so_out = torch.empty((L.NXROWS, n), dtype=dt, device=dev)
+        for label in ("all", "SOIL_M"):
+            mask = stateout.parse_groups(label)
+            nrow = len(stateout.rows(mask))
+            cases.append(("state_output", label,
+                          lambda mask=mask, nrow=nrow: eng.state_output(so_cs[prec], mask,
+                                                                        so_out[:nrow], -9999.0),
+                          n * stateout.algorithmic_bytes(mask, prec)))
         for name, order, fn, nbytes in cases:
             ms = timed(fn, a.reps)
             gbs = nbytes / (ms * 1e-3) / 1e9

@@ -30,6 +30,9 @@ downscaling, against the same values fed as pre-regridded model-grid files
 --interp-runs N times interpolation between input times instead: the same case
 with 3-hourly files, N fresh runs each with interp=True and without (the held
 path), interleaved -- ms per step of every run, median and range per variant.
+
+--state-out-runs N times state output instead: N fresh runs each with
+state_out="all" and without, interleaved, reported the same way.
 """
 import argparse
 import json
@@ -198,8 +201,40 @@ def interp_runs(a, nml):
             "summary": summary, "driver": runs["held"] + runs["interp"]}
 
 
+def state_out_runs(a, nml):
+    """The case as it is: fresh runs with state_out="all" (nmp_state_output on
+    the 8 output steps, 55 grids per LDASOUT file) and without (16 grids),
+    interleaved; ms per step of each run, and each variant's median and
+    range."""
+    import make_offline_case
+    make_offline_case.main([nml, "--ny", str(a.ny), "--nx", str(a.nx), "--kind", "mixed"])
+    cfg = config.Config(nml)
+    runs = {"plain": [], "state_out": []}
+    for i in range(a.state_out_runs):
+        for name, kw in (("plain", {}), ("state_out", dict(state_out="all"))):
+            r, _, drv = time_driver(cfg, 4, True, a.warm, a.steps, a.threads, "device", True, **kw)
+            r["variant"], r["round"] = name, i
+            r["pcie_down_bytes_per_output_step"] = len(drv.out_names) * 4 * drv.cs.ncol
+            print(json.dumps(r), flush=True)
+            runs[name].append(r)
+            del drv
+    summary = {}
+    for name, rs in runs.items():
+        ms = sorted(r["ms_per_step"] for r in rs)
+        summary[name] = {"runs": len(ms), "median_ms_per_step": float(np.median(ms)),
+                         "min_ms_per_step": ms[0], "max_ms_per_step": ms[-1]}
+    print(json.dumps(summary), flush=True)
+    return {"case": f"{a.ny} x {a.nx} land points (mixed USGS/STAS columns), 900-s steps, "
+                    "hourly LDASIN, 3-hourly LDASOUT; fp32, file bytes ingested on the device; "
+                    "fresh drivers, variants interleaved",
+            "summary": summary, "driver": runs["plain"] + runs["state_out"]}
+
+
 def main():
     ap = argparse.ArgumentParser()
+    ap.add_argument("--state-out-runs", type=int, default=0, metavar="N",
+                    help="time N fresh runs each with and without state_out='all', interleaved, "
+                         "instead")
     ap.add_argument("--interp-runs", type=int, default=0, metavar="N",
                     help="time N fresh runs each with and without interp on 3-hourly files, "
                          "interleaved, instead")
@@ -216,8 +251,8 @@ def main():
     a = ap.parse_args()
     os.makedirs(a.dir, exist_ok=True)
     nml = write_namelist(a.dir)
-    if a.interp_runs:
-        res = interp_runs(a, nml)
+    if a.interp_runs or a.state_out_runs:
+        res = interp_runs(a, nml) if a.interp_runs else state_out_runs(a, nml)
         if a.out:
             os.makedirs(os.path.dirname(os.path.abspath(a.out)), exist_ok=True)
             with open(a.out, "w") as f:
