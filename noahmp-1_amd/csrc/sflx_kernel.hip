@@ -226,7 +226,7 @@ template <class T, class D>
 DEV Sfc1Inv<T> sfc1_inv(D& d, T sfctmp, T qair, T rhoair, T zlvl, T zpd, T z0h) {
   const T tvir = (L(1.0) + L(0.61) * qair) * sfctmp;
   Sfc1Inv<T> v;
-  v.kgtv = KARMAN * d.divk(GRAV, d.rec(tvir));
+  v.kgtv = KARMAN * d.divn(GRAV, d.rec(tvir));
   v.rhocp = d.rec(rhoair * CPAIR);
   v.dz = zlvl - zpd;
   v.d2 = L(2.0) + z0h;
@@ -255,14 +255,14 @@ DEV bool sfcdif1(D& d, const Sfc1Inv<T>& inv, int iter, T h, const Sfc1Logs<T, R
     moz = L(0.0);
     moz2 = L(0.0);
   } else {
-    T tmp1 = d.div(inv.kgtv * h, inv.rhocp);
+    T tmp1 = d.divn(inv.kgtv * h, inv.rhocp);
     if (fabs(tmp1) <= mpe) tmp1 = mpe;
-    const Recip<T> rmol = d.rec(d.div(L(-1.0) * p3(fv), d.rec(tmp1)));
-    moz = rmin(d.divk(inv.dz, rmol), L(1.0));
+    const Recip<T> rmol = d.rec(d.divn(L(-1.0) * p3(fv), d.rec(tmp1)));
+    moz = rmin(d.divn(inv.dz, rmol), L(1.0));
     // the 2-m height's MOZ2 -> FM2/FH2 chain feeds only the 2-m diagnostics
     // (CHV2/CHB2 -> T2M, Q2): skipped when the step writes no diagnostics
     // (two_m false, wave-uniform), which changes no state value
-    moz2 = two_m ? rmin(d.divk(inv.d2, rmol), L(1.0)) : L(0.0);
+    moz2 = two_m ? rmin(d.divn(inv.d2, rmol), L(1.0)) : L(0.0);
   }
   if (mozold * moz < L(0.0)) mozsgn = mozsgn + 1;
   if (mozsgn >= 2) {
@@ -320,8 +320,8 @@ DEV bool sfcdif1(D& d, const Sfc1Inv<T>& inv, int iter, T h, const Sfc1Logs<T, R
   if (fabs(chfh) <= mpe) chfh = mpe;
   if (fabs(cm2fm2) <= mpe) cm2fm2 = mpe;
   if (fabs(ch2fh2) <= mpe) ch2fh2 = mpe;
-  cm = d.divk(KARMAN * KARMAN, d.rec(cmfm * cmfm));
-  ch = d.divk(KARMAN * KARMAN, d.rec(cmfm * chfh));
+  cm = d.divn(KARMAN * KARMAN, d.rec(cmfm * cmfm));
+  ch = d.divn(KARMAN * KARMAN, d.rec(cmfm * chfh));
   fv = ur * d.sqrt(cm);  // CM in the proof's interval (tools/div_proof.py)
   return win;
 }
@@ -419,20 +419,20 @@ DEV bool ragrb(D& d, const Recip<T>& rhocp, const Recip<T>& rhcan, T dzg, T sqrt
   constexpr bool kInRange = !std::is_same<M, Mth<T, R>>::value;
   T mozg = L(0.0);
   if (iter > 1) {
-    T tmp1 = d.div(KARMAN * d.divk(GRAV, d.rec(tah)) * hg, rhocp);
+    T tmp1 = d.divn(KARMAN * d.divn(GRAV, d.rec(tah)) * hg, rhocp);
     if (fabs(tmp1) <= mpe) tmp1 = mpe;
-    const T molg = d.div(L(-1.) * p3(fv), d.rec(tmp1));
-    mozg = rmin(d.divk(dzg, d.rec(molg)), L(1.0));
+    const T molg = d.divn(L(-1.) * p3(fv), d.rec(tmp1));
+    mozg = rmin(d.divn(dzg, d.rec(molg)), L(1.0));
   }
   T fhgnew = (mozg < L(0.0)) ? M::pow_mq(L(1.0) - L(15.0) * mozg) : L(1.0) + L(4.7) * mozg;
   fhg = (iter == 1) ? fhgnew : L(0.5) * (fhg + fhgnew);
   T cwpc = d.sqrt(cwp * vai * hcan * fhg);  // proven range (tools/div_proof.py)
-  T tmp1 = M::exp(d.div(-cwpc * z0hg, rhcan));
-  T tmp2 = M::exp(d.div(-cwpc * (z0h + zpd), rhcan));
-  T tmprah2 = d.div(hcan * M::exp(cwpc), d.rec(cwpc)) * (tmp1 - tmp2);
+  T tmp1 = M::exp(d.divn(-cwpc * z0hg, rhcan));
+  T tmp2 = M::exp(d.divn(-cwpc * (z0h + zpd), rhcan));
+  T tmprah2 = d.divn(hcan * M::exp(cwpc), d.rec(cwpc)) * (tmp1 - tmp2);
   T kh = rmax(KARMAN * fv * (hcan - zpd), mpe);
-  rahg = d.div(tmprah2, d.rec(kh));
-  T tmprb = d.div(cwpc * L(50.0), d.rec(L(1.0) - M::exp(-cwpc / L(2.0))));
+  rahg = d.divn(tmprah2, d.rec(kh));
+  T tmprb = d.divn(cwpc * L(50.0), d.rec(L(1.0) - M::exp(-cwpc / L(2.0))));
   rb = tmprb * sqrt_dleaf_uc;
   if constexpr (kInRange) return mozg >= (T)NMP_DOM_MOZG_LO;
   return true;
@@ -494,23 +494,23 @@ DEV void stomata_solve(D& d, const VegRec& V, const StomataPre<T>& p, T igs, T s
     T ci = L(0.5) * (cihigh + cilow);
     T wc = (T)NAN, wj = (T)NAN, we = (T)NAN;  // SAVEd nan4 init (func.f90:3854-3856)
     if (c3c4 == 1) {
-      wj = d.div(rmax(ci - cp, L(0.0)) * j, d.rec(ci + L(2.0) * cp));
-      wc = d.div(rmax(ci - cp, L(0.0)) * vcmx, d.rec(ci + awc));
+      wj = d.divn(rmax(ci - cp, L(0.0)) * j, d.rec(ci + L(2.0) * cp));
+      wc = d.divn(rmax(ci - cp, L(0.0)) * vcmx, d.rec(ci + awc));
       we = L(0.5) * vcmx;
     } else if (c3c4 == 2) {
       wj = j;
       wc = vcmx;
-      we = d.div(L(4000.0) * vcmx * ci, d.rec(sfcprs));
+      we = d.divn(L(4000.0) * vcmx * ci, d.rec(sfcprs));
     }
     psn = rmin(rmin(wj, wc), we) * igs;
     T cs = rmax(co2 - L(1.37) * rlb * sfcprs * psn, MPE);
-    T a = d.div(mp * psn * sfcprs * ea, d.rec(cs * ei)) + bp;
-    T b = (d.div(mp * psn * sfcprs, d.rec(cs)) + bp) * rlb - L(1.0);
+    T a = d.divn(mp * psn * sfcprs * ea, d.rec(cs * ei)) + bp;
+    T b = (d.divn(mp * psn * sfcprs, d.rec(cs)) + bp) * rlb - L(1.0);
     T c = -rlb;
     T q = (b >= L(0.0)) ? L(-0.5) * (b + d.sqrt(b * b - L(4.0) * a * c))
                         : L(-0.5) * (b - d.sqrt(b * b - L(4.0) * a * c));
-    T r1 = d.div(q, d.rec(a));
-    T r2 = d.div(c, d.rec(q));
+    T r1 = d.divn(q, d.rec(a));
+    T r2 = d.divn(c, d.rec(q));
     rs = rmax(r1, r2);
     T fci = rmax(cs - psn * sfcprs * L(1.65) * rs, L(0.0));
     if (((cihigh - cilow) <= CIERR) || fabs(fci - ci) <= MPE) break;
@@ -1419,7 +1419,9 @@ DEV void sflx_column(const DevParams& P, const KArgs<T>& A, Col<T>& c, const Sin
     // fails every comparison.
     auto vege_domain_ok = [&]() -> bool {
       auto in = [](T x, double lo, double hi) { return x >= (T)lo && x <= (T)hi; };
-      auto zero_or = [&](T x, double lo, double hi) { return x == L(0.0) || in(x, lo, hi); };
+      // (+0, the bit pattern: these are numerators of fix-up-free quotients,
+      // which must never be -0; a -0 here sends the lane to the IEEE loop)
+      auto zero_or = [&](T x, double lo, double hi) { return is_pzero(x) || in(x, lo, hi); };
       bool k = true;
       NMP_DOM(k, 0, in(c.sfctmp, NMP_DOM_T_LO, NMP_DOM_T_HI) & in(c.tg, NMP_DOM_T_LO, NMP_DOM_T_HI));
       NMP_DOM(k, 1, in(qair, 0.0, 1.0) & in(rhoair, NMP_DOM_RHO_LO, NMP_DOM_RHO_HI));
@@ -1505,7 +1507,7 @@ DEV void sflx_column(const DevParams& P, const KArgs<T>& A, Col<T>& c, const Sin
           chv = chv / ur;
           cmv = cmv / ur;
         }
-        rahc = rmax(L(1.0), d.divk(L(1.0), d.rec(chv * ur)));
+        rahc = rmax(L(1.0), d.divn(L(1.0), d.rec(chv * ur)));
         const Recip<T> rrahc = d.rec(rahc);  // RAWC = RAHC: CAH = CAW, H share it
         const bool wg = ragrb<T, R>(d, inv.rhocp, rhcan, dzg, sqrt_dleaf_uc, iter, vaie, hg, c.tah,
                                     zpd, z0mg, hcan, z0h, fv, cwp, mpe, fhg, rahg, rb);
@@ -1529,11 +1531,18 @@ DEV void sflx_column(const DevParams& P, const KArgs<T>& A, Col<T>& c, const Sin
               auto apar_ok = [&](T x) {
                 return x <= L(0.0) || in(x, NMP_DOM_APAR_LO, NMP_DOM_APAR_HI);
               };
+              // The bisection's quotients carry no fix-up (divn), so their
+              // numerators must never be -0: the zeros admitted here are +0
+              // (the bit pattern), VCMX25 and QE25 (0 in some tables) have
+              // their sign bits clear, and C3C4 is 1 or 2 (otherwise WJ, WC and
+              // WE stay NaN, outside divn's finite region).
               st_fast = V.stomata_fast && c.tv <= (T)NMP_DOM_STOMATA_TV_HI &&
-                        (c.eah == L(0.0) || in(c.eah, NMP_DOM_EAH_LO, NMP_DOM_EAH_HI)) &&
+                        (is_pzero(c.eah) || in(c.eah, NMP_DOM_EAH_LO, NMP_DOM_EAH_HI)) &&
                         in(c.co2air, NMP_DOM_CO2_LO, NMP_DOM_CO2_HI) &&
                         in(c.o2air, NMP_DOM_O2_LO, NMP_DOM_O2_HI) &&
-                        (sp.fnf == L(0.0) || in(sp.fnf, NMP_DOM_FNF_LO, 1.0)) &&
+                        (is_pzero(sp.fnf) || in(sp.fnf, NMP_DOM_FNF_LO, 1.0)) &&
+                        !__builtin_signbit((T)V.vcmx25) && !__builtin_signbit((T)V.qe25) &&
+                        (V.c3c4 == 1 || V.c3c4 == 2) &&
                         apar_ok(parsun) && apar_ok(parsha);
 #ifdef NMP_COUNT_FALLBACK
               if (!st_fast && (parsun > L(0.0) || parsha > L(0.0)))
@@ -1560,27 +1569,30 @@ DEV void sflx_column(const DevParams& P, const KArgs<T>& A, Col<T>& c, const Sin
           if constexpr (kFast)
             NMP_DOM(ok, 17, in(rssun, L(0.0), (T)NMP_DOM_RS_HI) & in(rssha, L(0.0), (T)NMP_DOM_RS_HI));
         }
-        cah = d.divk(L(1.0), rrahc);
-        cvh = d.divk(two_vaie, rrb);
-        T cgh = d.divk(L(1.0), rrahg);
+        // Every quotient but EVC and TR is formed without the fix-up (divn):
+        // tools/div_proof.py shows each numerator never -0.  EVC and TR keep it
+        // (div): CEW or CTW = +0 times a negative ESTV - EAH (dew) is -0.
+        cah = d.divn(L(1.0), rrahc);
+        cvh = d.divn(two_vaie, rrb);
+        T cgh = d.divn(L(1.0), rrahg);
         T cond = cah + cvh + cgh;
         const Recip<T> rcond = d.rec(cond);
-        T ata = d.div(c.sfctmp * cah + tgv * cgh, rcond);
-        T bta = d.div(cvh, rcond);
+        T ata = d.divn(c.sfctmp * cah + tgv * cgh, rcond);
+        T bta = d.divn(cvh, rcond);
         T csh = (L(1.0) - bta) * rhoair * CPAIR * cvh;
-        T caw = d.divk(L(1.0), rrahc);
-        T cew = d.divk(fwet_vaie, rrb);
+        T caw = d.divn(L(1.0), rrahc);
+        T cew = d.divn(fwet_vaie, rrb);
         T ctw = (L(1.0) - c.fwet) *
-                (d.divk(laisune, d.rec(rb + rssun)) + d.divk(laishae, d.rec(rb + rssha)));
-        T cgw = d.divk(L(1.0), d.rec(rahg + rsurf));
+                (d.divn(laisune, d.rec(rb + rssun)) + d.divn(laishae, d.rec(rb + rssha)));
+        T cgw = d.divn(L(1.0), d.rec(rahg + rsurf));
         cond = caw + cew + ctw + cgw;
         const Recip<T> rcond2 = d.rec(cond);
-        T aea = d.div(eair * caw + estg * cgw, rcond2);
-        T bea = d.div(cew + ctw, rcond2);
-        T cev = d.div((L(1.0) - bea) * cew * rhoair * CPAIR, rgammav);
+        T aea = d.divn(eair * caw + estg * cgw, rcond2);
+        T bea = d.divn(cew + ctw, rcond2);
+        T cev = d.divn((L(1.0) - bea) * cew * rhoair * CPAIR, rgammav);
         const T ctr_n = (L(1.0) - bea) * ctw * rhoair * CPAIR;
         if constexpr (kFast) NMP_DOM(ok, 26, nwin(ctr_n));
-        T ctr = d.div(ctr_n, rgammav);
+        T ctr = d.divn(ctr_n, rgammav);
         c.tah = ata + bta * c.tv;
         c.eah = aea + bea * estv;
         irc = fveg * (air + cir * p4(c.tv));
@@ -1593,15 +1605,15 @@ DEV void sflx_column(const DevParams& P, const KArgs<T>& A, Col<T>& c, const Sin
         T b = sav - irc - shc - evc - tr;
         T a = fveg * (L(4.0) * cir * p3(c.tv) + csh + (cev + ctr) * destv);
         if constexpr (kFast) NMP_DOM(ok, 28, nwin(b));
-        T dtv = d.div(b, d.rec(a));
+        T dtv = d.divn(b, d.rec(a));
         irc = irc + fveg * L(4.0) * cir * p3(c.tv) * dtv;
         shc = shc + fveg * csh * dtv;
         evc = evc + fveg * cev * destv * dtv;
         tr = tr + fveg * ctr * destv * dtv;
         c.tv = c.tv + dtv;
-        h = d.div(rhoair * CPAIR * (c.tah - c.sfctmp), rrahc);
-        hg = d.div(rhoair * CPAIR * (tgv - c.tah), rrahg);
-        c.qsfc = d.div(L(0.622) * c.eah, d.rec(c.sfcprs - L(0.378) * c.eah));
+        h = d.divn(rhoair * CPAIR * (c.tah - c.sfctmp), rrahc);
+        hg = d.divn(rhoair * CPAIR * (tgv - c.tah), rrahg);
+        c.qsfc = d.divn(L(0.622) * c.eah, d.rec(c.sfcprs - L(0.378) * c.eah));
         return dtv;
       };
       if constexpr (kFast) NMP_DOM(ok, 18, in(c.tv, (T)NMP_DOM_T_LO, (T)NMP_DOM_T_HI));
@@ -1624,7 +1636,11 @@ DEV void sflx_column(const DevParams& P, const KArgs<T>& A, Col<T>& c, const Sin
       // outside their window repeats the loop from its start with IEEE
       // division (TV/TAH/EAH reloaded: nothing has stored them yet)
       DivFast32 df;
-      if (!vege_domain_ok() || !vege_loop(df)) {
+      const bool fast_ok = vege_domain_ok() && vege_loop(df);
+#ifdef NMP_COUNT_FALLBACK
+      df.flush(fast_ok);  // divn's counters: only of a loop whose results are kept
+#endif
+      if (!fast_ok) {
 #ifdef NMP_COUNT_FALLBACK
         atomicAdd(&nmp_fallback_ctr, 1u);
         for (int b = 0; b < 34; ++b)
@@ -1745,13 +1761,13 @@ DEV void sflx_column(const DevParams& P, const KArgs<T>& A, Col<T>& c, const Sin
             chb = rmin(L(0.01), chb);
           }
         }
-        T rahb = rmax(L(1.0), d.divk(L(1.0), d.rec(chb * ur)));
+        T rahb = rmax(L(1.0), d.divn(L(1.0), d.rec(chb * ur)));
         const Recip<T> rrahb = d.rec(rahb);  // RAWB = RAHB
-        ehb = d.divk(L(1.0), rrahb);
+        ehb = d.divn(L(1.0), rrahb);
         estg = es_tgb;
         const T destg = des_tgb;
-        csh = d.div(rhoair * CPAIR, rrahb);
-        cev = d.div(d.div(rhoair * CPAIR, d.rec(gammag)), d.rec(rsurf + rahb));
+        csh = d.divn(rhoair * CPAIR, rrahb);
+        cev = d.divn(d.divn(rhoair * CPAIR, d.rec(gammag)), d.rec(rsurf + rahb));
         irb = cir * p4(tgb) - emg * c.lwdn;
         shb = csh * (tgb - c.sfctmp);
         evb = cev * (estg * rhsur - eair);
@@ -1759,7 +1775,7 @@ DEV void sflx_column(const DevParams& P, const KArgs<T>& A, Col<T>& c, const Sin
         T b = sag - irb - shb - evb - ghb;
         T a = L(4.0) * cir * p3(tgb) + csh + cev * destg + cgh;
         if constexpr (kFast) NMP_DOM(ok, 29, nwin(b));
-        T dtg = d.div(b, d.rec(a));
+        T dtg = d.divn(b, d.rec(a));
         irb = irb + L(4.0) * cir * p3(tgb) * dtg;
         shb = shb + csh * dtg;
         evb = evb + cev * destg * dtg;
@@ -1794,7 +1810,14 @@ DEV void sflx_column(const DevParams& P, const KArgs<T>& A, Col<T>& c, const Sin
     DivRef<T> drb;
     if constexpr (sizeof(T) == 4 && R && OS != 0) {
       DivFast32 dfb;
-      if (!bare_domain_ok() || !bare_loop(dfb)) {
+#ifdef NMP_COUNT_FALLBACK
+      dfb.grp = NMP_DIVN_BARE;
+#endif
+      const bool fast_ok = bare_domain_ok() && bare_loop(dfb);
+#ifdef NMP_COUNT_FALLBACK
+      dfb.flush(fast_ok);
+#endif
+      if (!fast_ok) {
 #ifdef NMP_COUNT_FALLBACK
         atomicAdd(&nmp_fallback_ctr, 1u);
         for (int b = 20; b < 35; ++b)
@@ -2696,12 +2719,16 @@ DEV void sflx_column(const DevParams& P, const KArgs<T>& A, Col<T>& c, const Sin
     // a normal quotient (tools/fdiv_exhaust.hip).  The thicknesses are checked
     // here once against [2^-20, 2^20]; the numerators (WDF * DDZ of very dry
     // soil is ~1e-32, WFLUX may cancel) are checked per division against
-    // a = 0 or [2^-102, 2^100], so the quotient lies in [2^-122, 2^120]
-    // (tools/div_proof.py soil_sites).  A lane outside takes IEEE division
-    // (an exec-masked branch that no lane usually enters).
+    // a = +0 (the bit pattern) or [2^-102, 2^100], so the quotient lies in
+    // [2^-122, 2^120] (tools/div_proof.py soil_sites) and, the numerator never
+    // being -0 there, needs no fix-up (divn).  A lane outside takes IEEE
+    // division (an exec-masked branch that no lane usually enters).
     constexpr bool kSoilFast = sizeof(T) == 4 && R && OS != 0;
     typedef std::conditional_t<kSoilFast, DivFast32, DivRef<T>> SoilDiv;
-    const SoilDiv sd;
+    SoilDiv sd;
+#ifdef NMP_COUNT_FALLBACK
+    if constexpr (kSoilFast) sd.grp = NMP_DIVN_SOIL;
+#endif
     Recip<T> rtemp[3], rden[4], rnden[4];
     bool soil_ok = true;
 #pragma unroll
@@ -2718,13 +2745,14 @@ DEV void sflx_column(const DevParams& P, const KArgs<T>& A, Col<T>& c, const Sin
     }
     auto sdv = [&](T a, const Recip<T>& rb) -> T {
       if constexpr (kSoilFast) {
-        T q = sd.div(a, rb);
+        T q = sd.divn(a, rb);
         const T m = fabs(a);
-        const bool in = a == L(0.0) || (m >= L(0x1p-102) && m <= L(0x1p+100));  // NaN: out
+        const bool in = is_pzero(a) || (m >= L(0x1p-102) && m <= L(0x1p+100));  // NaN, -0: out
         if (__builtin_expect(!soil_ok || !in, 0)) {
           q = a / rb.b;
 #ifdef NMP_COUNT_FALLBACK
           atomicAdd(&nmp_fb_reason[25], 1u);  // soil-water division on IEEE
+          sd.drop_last();                     // (its divn quotient is not used)
 #endif
         }
         return q;
@@ -2836,6 +2864,9 @@ DEV void sflx_column(const DevParams& P, const KArgs<T>& A, Col<T>& c, const Sin
       rsat = rsat + wplus;
       qdrain_save = qdrain_save + qdrain;
     }
+#ifdef NMP_COUNT_FALLBACK
+    if constexpr (kSoilFast) sd.flush(true);
+#endif
     qdrain = qdrain_save / (T)niter;
     runsrf = runsrf * L(1000.0) + rsat * L(1000.0) / DT;
     qdrain = qdrain * L(1000.0);

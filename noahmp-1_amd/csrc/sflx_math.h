@@ -133,6 +133,13 @@ template <class T>
 __device__ __forceinline__ T rmax(T a, T b) { return a > b ? a : b; }
 template <class T>
 __device__ __forceinline__ T rmin(T a, T b) { return a < b ? a : b; }
+// x is +0: the bit pattern, so -0 is not (the tests that admit "0 or in range"
+// numerators to DivFast32::divn, which needs a numerator that is never -0)
+template <class T>
+__device__ __forceinline__ bool is_pzero(T x) {
+  if constexpr (sizeof(T) == 4) return __builtin_bit_cast(uint32_t, x) == 0u;
+  else return __builtin_bit_cast(uint64_t, x) == 0ull;
+}
 // integer powers as the reference's compiler lowers them: sequential products
 template <class T>
 __device__ __forceinline__ T p2(T x) { return x * x; }
@@ -205,6 +212,7 @@ struct DivRef {
   __device__ __forceinline__ Recip<T> rec(T b) const { return {b, b}; }
   __device__ __forceinline__ T div(T a, const Recip<T>& R) const { return dv(a, R.b); }
   __device__ __forceinline__ T divk(T a, const Recip<T>& R) const { return dv(a, R.b); }
+  __device__ __forceinline__ T divn(T a, const Recip<T>& R) const { return dv(a, R.b); }
   __device__ __forceinline__ void chk(T) const {}
   // the reference's SQRT: IEEE correctly rounded
   __device__ __forceinline__ static T sqrt(T x) {
@@ -243,7 +251,36 @@ __device__ __forceinline__ float sqrt_normal32(float x) {
 // exponent edges, tests/test_gpu_routines.py).  The region stops short of
 // FLT_MAX on purpose: for quotients within an ulp or two of it the product
 // a*r can round past FLT_MAX and the sequence differs.
+#ifdef NMP_COUNT_FALLBACK
+// the counters of the counting builds: 0..39 sflx_kernel.hip's fallback
+// reasons, 40..49 MthGuard32's calls, 50..57 DivFast32::divn's quotients
+static __device__ unsigned int nmp_fb_reason[64];
+// divn's groups of sites: the canopy loop (with its sfcdif1, ragrb and stomata
+// bisection), the bare loop (with its sfcdif1), the soil sub-steps, atanf_ge1
+enum { NMP_DIVN_CANOPY = 0, NMP_DIVN_BARE, NMP_DIVN_SOIL, NMP_DIVN_ATAN };
+#endif
 struct DivFast32 {
+#ifdef NMP_COUNT_FALLBACK
+  // The counting build forms the fix-up's result beside every divn quotient
+  // and counts, per lane, the quotients formed and those whose bits the fix-up
+  // would have changed.  The caller adds them to the group's counters
+  // (nmp_fb_reason[50 + 2 grp], [51 + 2 grp]) once it knows that the lane keeps
+  // the quotients: flush(ok) after a Newton loop, drop_last() on the soil
+  // sub-steps' IEEE arm.  atanf_ge1's functor has no caller to do so and adds
+  // at once, discarded loops included.
+  int grp = NMP_DIVN_CANOPY;
+  mutable unsigned nf = 0, nc = 0;
+  mutable bool last = false;
+  __device__ __forceinline__ void flush(bool keep) const {
+    if (keep && nf) atomicAdd(&nmp_fb_reason[50 + 2 * grp], nf);
+    if (keep && nc) atomicAdd(&nmp_fb_reason[51 + 2 * grp], nc);
+    nf = nc = 0;
+  }
+  __device__ __forceinline__ void drop_last() const {
+    nf -= 1;
+    nc -= last;
+  }
+#endif
   __device__ __forceinline__ static float recip(float b) {
     float r = __builtin_amdgcn_rcpf(b);
     const float e = __builtin_fmaf(-b, r, 1.0f);
@@ -257,6 +294,30 @@ struct DivFast32 {
     return __builtin_amdgcn_div_fixupf(q, R.b, a);
   }
   __device__ __forceinline__ float divk(float a, const Recip<float>& R) const { return div(a, R); }
+  // a/b without the closing v_div_fixup_f32.  Region: DivFast32's (|b| in
+  // [2^-126, 2^126], a = 0 or |a| >= 2^-102, |a/b| in [2^-126, 2^126]), both
+  // operands finite, and a never -0.  There the fix-up is the identity: for
+  // a != 0 the fma already carries the quotient's sign, +0 / b gives +0 for
+  // b > 0 and -0 for b < 0, and -0 / b gives +0 for b < 0.  The one case it
+  // changed is a = -0 with b > 0, where this returns +0 and IEEE -0
+  // (tests/test_gpu_div_nofix.py pins all four); tools/div_proof.py tracks the
+  // sign of every numerator's zero and declares which sites may call this.
+  // NaN or infinite operands give NaN here where the fix-up gave IEEE's
+  // infinity: only lanes already outside a window see them, and their loop is
+  // discarded.
+  __device__ __forceinline__ float divn(float a, const Recip<float>& R) const {
+    float q = a * R.r;
+    const float e = __builtin_fmaf(-R.b, q, a);
+    q = __builtin_fmaf(e, R.r, q);
+#ifdef NMP_COUNT_FALLBACK
+    const float qf = __builtin_amdgcn_div_fixupf(q, R.b, a);
+    last = __builtin_bit_cast(uint32_t, qf) != __builtin_bit_cast(uint32_t, q);
+    nf += 1;
+    nc += last;
+    if (grp == NMP_DIVN_ATAN) flush(true);
+#endif
+    return q;
+  }
   __device__ __forceinline__ void chk(float) const {}
   // at the range-proven sqrt sites (tools/div_proof.py): x finite and >= 2^-96
   __device__ __forceinline__ static float sqrt(float x) { return sqrt_normal32(x); }
@@ -282,8 +343,11 @@ struct MthInRange32 : Mth<float, true> {
   NMP_MATH_FN float pow_mq(float x) { return gm::powf_inrange(x, -0.25f, gm_lds); }
   struct Div {
     __device__ __forceinline__ float operator()(float a, float b) const {
-      const DivFast32 d;
-      return d.div(a, d.rec(b));
+      DivFast32 d;  // the numerator is never -0 (tools/div_proof.py)
+#ifdef NMP_COUNT_FALLBACK
+      d.grp = NMP_DIVN_ATAN;
+#endif
+      return d.divn(a, d.rec(b));
     }
   };
   NMP_MATH_FN float atan(float x) { return gm::atanf_ge1(x, Div{}); }
@@ -318,10 +382,8 @@ struct LoopMth<float, true, DivFast32> {
 //          own functions in powf's order, the tail's overflow / underflow
 //          exits (reachable: 0.01**26 in dry soil) as selects.
 // NMP_COUNT_FALLBACK builds count, per function, the wave-level calls and
-// those that took the full function (nmp_fb_reason 40..49).
-#ifdef NMP_COUNT_FALLBACK
-static __device__ unsigned int nmp_fb_reason[64];
-#endif
+// those that took the full function (nmp_fb_reason 40..49, declared above
+// DivFast32).
 struct MthGuard32 : Mth<float, true> {
   // true when any active lane of the wave has `outside`; `slot`: the counters
   static __device__ __forceinline__ bool any_outside(bool outside, int slot) {

@@ -47,6 +47,27 @@ leaves through them.  None can be NaN: MOZ, MOZ2 and MOZG are MIN(quotient, 1),
 which maps NaN to 1 (a < b ? a : b), -inf fails the window, and FHG is an
 average of values in (0, 5.7].
 
+The sign of zero.  DivFast32::divn (csrc/sflx_math.h) is the same sequence
+without the closing v_div_fixup_f32.  Inside the region above the fix-up is the
+identity for every nonzero numerator and for a = +0; for a = -0 the sequence
+gives -0 when b < 0 (as IEEE) and +0 when b > 0 (IEEE: -0).  A site may drop
+the fix-up when its numerator is never -0.  So besides magnitudes every value
+carries the signs its nonzero values can take (sg) and the signs its zero can
+take (zs), and the rules are the loop's own arithmetic in round-to-nearest:
+  x - y          its zero is +0, except (-0) - (+0) = -0
+  x + y          its zero is +0 unless both terms are -0
+  x * y          a zero takes the XOR of the factors' signs
+  -x             flips both
+  MAX(x, 0)      is >= +0 (a > b ? a : b with b = +0.0)
+  constants      carry their sign
+Inputs that the kernel admits as "0 or in [lo, hi]" (ZPD, LAISUNE, LAISHAE,
+FWET; the bisection's EAH and FNF) are tested there against the bit pattern of
++0, so a -0 among them sends the lane to IEEE division; the soil sub-steps
+test every numerator the same way.  Every site is declared fix-up-free or not
+(`fix=True` keeps v_div_fixup_f32: DivFast32::div), the table prints the
+declaration beside "can the numerator be -0", and a site declared fix-up-free
+whose numerator can be -0 fails the script like one outside the region.
+
     python tools/div_proof.py            # prints the per-site table, exit 1 on a failure
 """
 import math
@@ -71,38 +92,81 @@ def domain():
     return d
 
 
-class M:
-    """|x| in [lo, hi] for x != 0; z: x may be 0."""
+POS, NEG, ANY = frozenset((1,)), frozenset((-1,)), frozenset((1, -1))
 
-    def __init__(self, lo, hi, z=False):
+
+class M:
+    """|x| in [lo, hi] for x != 0; z: x may be 0.  sg: the signs of its nonzero
+    values; zs: the signs of its zero (empty unless z)."""
+
+    def __init__(self, lo, hi, z=False, sg=POS, zs=None):
         assert 0 < lo <= hi, (lo, hi)
         self.lo, self.hi, self.z = lo * (1 - W), hi * (1 + W), z
+        self.sg = frozenset(sg)
+        self.zs = frozenset(POS if zs is None else zs) if z else frozenset()
+
+    def full(self):          # every sign the value can carry, zero included
+        return self.sg | self.zs
 
     def __mul__(self, o):
-        o = o if isinstance(o, M) else M(abs(o), abs(o))
-        return M(self.lo * o.lo, self.hi * o.hi, self.z or o.z)
+        o = o if isinstance(o, M) else c(o)
+        sg = {a * b for a in self.sg for b in o.sg}
+        zs = {a * b for a in self.zs for b in o.full()} | {a * b for a in self.full() for b in o.zs}
+        return M(self.lo * o.lo, self.hi * o.hi, self.z or o.z, sg, zs)
 
     __rmul__ = __mul__
 
+    def __neg__(self):
+        return M(self.lo / (1 - W), self.hi / (1 + W), self.z, {-a for a in self.sg},
+                 {-a for a in self.zs})
+
     def __add__(self, o):   # terms of one sign (all >= 0 here)
+        assert self.sg == POS and o.sg == POS, "sum of terms of one sign only"
         lo = min(self.lo, o.lo) if (self.z or o.z) else max(self.lo, o.lo)
-        return M(lo, self.hi + o.hi, self.z and o.z)
+        zs = set()
+        if self.z and o.z:   # a zero sum is +0 unless both terms are -0
+            if 1 in self.zs or 1 in o.zs:
+                zs.add(1)
+            if -1 in self.zs and -1 in o.zs:
+                zs.add(-1)
+        return M(lo, self.hi + o.hi, self.z and o.z, POS, zs)
 
     def nz(self):           # the same magnitudes, known nonzero
-        return M(self.lo, self.hi)
+        return M(self.lo, self.hi, False, self.sg)
+
+    def signed(self, src):  # these magnitudes with the signs derived for src
+        assert self.z or not src.z
+        return M(self.lo / (1 - W), self.hi / (1 + W), self.z, src.sg, src.zs if self.z else ())
+
+    def neg0(self):         # can the value be -0
+        return -1 in self.zs
 
     def __repr__(self):
         return f"{'0|' if self.z else ''}[{self.lo:.3g}, {self.hi:.3g}]"
 
 
 def c(v):
-    return M(abs(v), abs(v))
+    return M(abs(v), abs(v), False, POS if v > 0 else NEG)
 
 
 def diff(x, y):
-    """|x - y| for floats x, y with |x| <= x.hi etc.: 0 or >= 2^(E-23)."""
+    """|x - y| for floats x, y with |x| <= x.hi etc.: 0 or >= 2^(E-23).  Either
+    sign; a zero difference is +0 unless x is -0 and y is +0."""
     e = math.floor(math.log2(min(x.lo, y.lo)))
-    return M(2.0 ** (e - 23), x.hi + y.hi, True)
+    zs = {1} | ({-1} if (-1 in x.zs and 1 in y.zs) else set())
+    return M(2.0 ** (e - 23), x.hi + y.hi, True, ANY, zs)
+
+
+def max0(x):
+    """MAX(x, 0): rmax(a, b) = a > b ? a : b with b = +0.0 returns +0 for either zero."""
+    return M(x.lo / (1 - W), x.hi / (1 + W), True, POS, POS)
+
+
+def sgn(m):
+    s = {POS: "+", NEG: "-", ANY: "+-"}[m.sg]
+    if m.z:
+        s += " 0:" + {POS: "+0", NEG: "-0", ANY: "+-0"}[m.zs]
+    return s
 
 
 def fn(f, x):            # monotone increasing f on magnitudes
@@ -112,12 +176,18 @@ def fn(f, x):            # monotone increasing f on magnitudes
 rows, bad = [], []
 
 
-def site(name, a, b, ref, note=""):
-    """Record one division a/b; returns the quotient's magnitude interval."""
-    q = M(a.lo / b.hi, a.hi / b.lo, a.z)
+def site(name, a, b, ref, note="", fix=False):
+    """Record one division a/b; returns the quotient's magnitude interval and
+    signs.  fix: the site keeps v_div_fixup_f32 (DivFast32::div); otherwise it
+    is declared fix-up-free (DivFast32::divn) and its numerator must never be
+    -0."""
+    q = M(a.lo / b.hi, a.hi / b.lo, a.z, {x * y for x in a.sg for y in b.sg},
+          {x * y for x in a.zs for y in b.sg})
     ok = (not b.z and N_MIN <= b.lo and b.hi <= N_MAX and A_MIN <= a.lo
           and N_MIN <= q.lo and q.hi <= N_MAX)
-    rows.append((name, ref, a, b, q, ok, note))
+    if not fix and a.neg0():
+        ok = False
+    rows.append((name, ref, a, b, q, ok, note, fix))
     if not ok:
         bad.append(name)
     return q
@@ -129,7 +199,7 @@ def sqrt_site(name, x, ref, note=""):
     its zero / infinity / NaN select."""
     ok = not x.z and 2.0 ** -96 <= x.lo and x.hi <= 3.4028234e38
     rows.append((name, ref, x, M(1.0, 1.0), fn(math.sqrt, x), ok,
-                 ("sqrt: " + note) if note else "sqrt"))
+                 ("sqrt: " + note) if note else "sqrt", None))
     if not ok:
         bad.append(name)
 
@@ -188,7 +258,10 @@ def libm_sites(D, moz_static, moz2_static, mozg_static, cwpc, q14, q15):
     libm_site("libm: EXP(CWPC)", "expf", cwpc.lo, cwpc.hi, ":3336")
     libm_site("libm: EXP(-CWPC / 2)", "expf", -cwpc.hi / 2, -cwpc.lo / 2, ":3346")
     # atanf_ge1's division through DivFast32 (sflx_math.h MthInRange32::Div)
-    site("libm: ATAN's NUM / DEN", M(2.0 ** -23, 1.0, True), M(1.0, 2.0 ** 26), "atanf",
+    # num = x - 1 or x - 1.5: a float difference of nonzero terms, its zero is +0
+    x = M(1.0, 2.0 ** 25)
+    num = diff(x, c(1.5))
+    site("libm: ATAN's NUM / DEN", M(2.0 ** -23, 1.0, True).signed(num), M(1.0, 2.0 ** 26), "atanf",
          "den = x+1, 1+1.5x or x; num = x-1, x-1.5 (multiples of 2^-23) or -1")
 
 
@@ -223,8 +296,9 @@ def stomata_sites(D, T, p, es, rb):
     kc25, akc, ko25, ako, avcmx = box("KC25"), box("AKC"), box("KO25"), box("AKO"), box("AVCMX")
     vcmx25, qe25, mp, bp = box("VCMX25"), box("QE25"), box("MP"), box("BP")
     co2, o2 = M(*box("CO2")), M(*box("O2"))
-    apar, eah = M(*box("APAR")), M(D["EAH_LO"], D["EAH_HI"], True)
-    fnf = M(D["FNF_LO"], 1.0, True)
+    # EAH and FNF: "0 or in [lo, hi]", the 0 tested as the bit pattern of +0
+    apar, eah = M(*box("APAR")), M(D["EAH_LO"], D["EAH_HI"], True, POS, POS)
+    fnf = M(D["FNF_LO"], 1.0, True, POS, POS)
     btran = M(MPE, 1.0001)                        # MAX(MPE, sum of root-layer shares)
     cf = M(p.lo / (RGAS * T.hi) * 1e6, p.hi / (RGAS * T.lo) * 1e6)
     rlb = M(rb.lo / cf.hi, rb.hi / cf.lo)         # RLB = RB / CF (IEEE, stomata_pre)
@@ -250,11 +324,14 @@ def stomata_sites(D, T, p, es, rb):
         cp = M(0.105 * kc.lo * o2.lo / ko.hi, 0.105 * kc.hi * o2.hi / ko.lo)
         v_lo, v_hi = pw(avcmx, ex0, ex1)
         efac = M(1 + math.exp(g(t0)), 1 + math.exp(g(t1)))
+        # VCMX = VCMX25 / (...) * FNF * BTRAN * AVCMX**x and J = 4.6 APAR QE25: products
+        # of factors >= +0 (VCMX25, QE25: the kernel admits the type only with
+        # their sign bits clear; FNF above; APAR > 0 here), so their zero is +0
         vcmx = M(vcmx25[0] / efac.hi * fnf.lo * btran.lo * v_lo,
-                 vcmx25[1] / efac.lo * 1.0 * btran.hi * v_hi, True)
-        j = M(4.6 * apar.lo * qe25[0], 4.6 * apar.hi * qe25[1], True)
+                 vcmx25[1] / efac.lo * 1.0 * btran.hi * v_hi, True, POS, (fnf * btran).zs)
+        j = M(4.6 * apar.lo * qe25[0], 4.6 * apar.hi * qe25[1], True, POS, POS)
         ci = M(1.5 * co2.lo * 2.0 ** -20, 1.5 * co2.hi)   # bisection midpoints of [0, 1.5 CO2]
-        dci = diff(ci, cp)                        # MAX(CI - CP, 0): 0 or >= granularity
+        dci = max0(diff(ci, cp))                  # MAX(CI - CP, 0): +0 or >= granularity
         rows_before = len(rows)
         wj = site("stomata: WJ = (CI-CP)*J / (CI+2CP)", dci * j,
                   M(ci.lo + 2 * cp.lo, ci.hi + 2 * cp.hi), ":3860")
@@ -267,7 +344,11 @@ def stomata_sites(D, T, p, es, rb):
         # WC <= VCMX because (CI-CP) < CI+2CP and < CI+AWC (C3); WJ = J, WC =
         # VCMX (C4) -- a bound interval arithmetic on the quotients loses
         hi = min(j.hi, vcmx.hi)
-        psn = M(lo, hi, True)
+        # >= +0: rmin(a, b) = a < b ? a : b returns one of WJ, WC, WE, each >= +0
+        # (C3 and C4 alike; the kernel admits no other C3C4), times IGS = +0 or 1
+        assert not (wj.neg0() or wc.neg0() or we4.neg0() or we3.neg0())
+        assert wj.sg == wc.sg == we4.sg == we3.sg == POS
+        psn = M(lo, hi, True, POS, POS)
         cs = M(MPE, co2.hi)                       # MAX(CO2 - 1.37 RLB SFCPRS PSN, MPE)
         num = M(mp[0], mp[1]) * psn * p
         if t1 > D["TMIN_LO"]:
@@ -280,9 +361,9 @@ def stomata_sites(D, T, p, es, rb):
         bmag = M(1e-30, (xb.hi + bp[1]) * rlb.hi + 1.0, True)
         sqrt_site("stomata: SQRT(B*B - 4*A*C)", M(4 * a.lo * rlb.lo, bmag.hi ** 2 + 4 * a.hi * rlb.hi),
                   ":3873", "C = -RLB < 0, so the radicand is >= 4*A*RLB")
-        q = M(math.sqrt(a.lo * rlb.lo), bmag.hi + math.sqrt(a.hi * rlb.hi))
+        q = M(math.sqrt(a.lo * rlb.lo), bmag.hi + math.sqrt(a.hi * rlb.hi), False, ANY)
         site("stomata: R1 = Q / A", q, a, ":3875")
-        site("stomata: R2 = C / Q", rlb, q, ":3876", "C = -RLB")
+        site("stomata: R2 = C / Q", -rlb, q, ":3876", "C = -RLB")
         for r in rows[rows_before:]:
             name = r[0]
             if name not in worst or not r[5] or (worst[name][5] and r[4].lo < worst[name][4].lo):
@@ -304,11 +385,14 @@ def soil_sites():
     [2^-20, 2^20] (outside: every such division on IEEE).  Their numerators
     (2, 2*(SMX(K)-SMX(K+1)), WDF*DDZ, WFLUX) are not bounded away from 0 --
     WDF of very dry clay is ~1e-32 -- so the kernel checks each numerator at
-    run time: a = 0 or 2^-102 <= |a| <= 2^100, else that lane divides on IEEE.
+    run time: a = +0 (the bit pattern) or 2^-102 <= |a| <= 2^100, else that lane
+    divides on IEEE.
     Inside both checks the quotient lies in [2^-122, 2^120]."""
     den = M(2.0 ** -20, 2.0 ** 20)
-    num = M(A_MIN * (1 + 2 * W), 2.0 ** 100, True)  # (M widens its bounds by W)
-    note = "numerator window checked per lane, IEEE outside"
+    # (M widens its bounds by W); either sign, its zero the bit pattern of +0:
+    # the kernel's test, so a -0 numerator divides on IEEE
+    num = M(A_MIN * (1 + 2 * W), 2.0 ** 100, True, ANY, POS)
+    note = "numerator window and +0 checked per lane, IEEE outside"
     site("soil: DDZ = 2 / TEMP1", c(2.0), den, ":6243")
     site("soil: DSMDZ = 2*(SMX(K)-SMX(K+1)) / TEMP1", num, den, ":6244", note)
     site("soil: AI, CI, BI = -WDF*DDZ / DENOM", num, den, ":6266-6272", note)
@@ -329,11 +413,12 @@ def main():
     z0 = M(D["Z0_LO"], D["Z0_HI"])                 # Z0M = Z0H, Z0MG
     d2 = M(2.0, 2.0 + D["Z0_HI"])                  # 2 + Z0H
     hcan = M(D["HCAN_LO"], D["HCAN_HI"])
-    zpd = M(D["Z0_LO"], D["HCAN_HI"], True)        # 0 or >= Z0_LO, <= HCAN
+    # "0 or in [lo, hi]" inputs: the kernel tests the 0 as the bit pattern of +0
+    zpd = M(D["Z0_LO"], D["HCAN_HI"], True, POS, POS)  # +0 or >= Z0_LO, <= HCAN
     cwph = M(D["CWPH_LO"], D["CWPH_HI"])           # CWP * VAIE * HCAN
     vaie = M(D["VAI_LO"], 6.0)
-    lai = M(D["LAI_LO"], 6.0, True)
-    fwet = M(D["FWET_LO"], 1.0, True)
+    lai = M(D["LAI_LO"], 6.0, True, POS, POS)
+    fwet = M(D["FWET_LO"], 1.0, True, POS, POS)
     fveg = M(D["FVEG_LO"], 1.0)
     sdl = M(D["SDL_LO"], D["SDL_HI"])              # SQRT(DLEAF/UC)
     rsurf_hi = D["RSURF_HI"]
@@ -351,16 +436,18 @@ def main():
     cm = M(0.16 / cmfm.hi ** 2, 0.16 / cmfm.lo ** 2)
     fv = ur * fn(math.sqrt, cm)                     # FV = UR * SQRT(CM)
     rahc = M(1.0, 1.0 / (cm.lo * ur.lo))            # MAX(1, 1/(CH*UR))
-    h = M((rhocp * dT).lo / rahc.hi, (rhocp * dT).hi, True)
-    hg = M((rhocp * dT).lo / rahg_w.hi, (rhocp * dT).hi / rahg_w.lo, True)
+    # either sign; their zero is +0: the loop starts them at +0.0 and ends an
+    # iteration with (RHOAIR*CPAIR*difference) / positive (checked below)
+    h = M((rhocp * dT).lo / rahc.hi, (rhocp * dT).hi, True, ANY, POS)
+    hg = M((rhocp * dT).lo / rahg_w.hi, (rhocp * dT).hi / rahg_w.lo, True, ANY, POS)
     fhg_lo = None                                   # derived below, then checked
 
     # ---- sfcdif1 (iter >= 2), :3405-3441, sflx_kernel.hip sfcdif1 ----
     kgtv = KARMAN * site("GRAV / TVIR", c(GRAV), tvir, ":3430 (once per loop)")
     tmp1 = site("TMP1 = KGTV*H / RHOCP", kgtv * h, rhocp, ":3431")
-    tmp1 = M(1e-6, tmp1.hi)                         # IF (ABS(TMP1) <= MPE) TMP1 = MPE
+    tmp1 = M(1e-6, tmp1.hi, False, ANY)             # IF (ABS(TMP1) <= MPE) TMP1 = MPE
     fv3 = fn(lambda x: x ** 3, fv)
-    mol = site("MOL = -FV**3 / TMP1", fv3, tmp1, ":3433")
+    mol = site("MOL = -FV**3 / TMP1", -fv3, tmp1, ":3433")
     moz_q = site("MOZ = (ZLVL-ZPD) / MOL", dz, mol, ":3434", "then MIN(., 1)")
     moz2_q = site("MOZ2 = (2+Z0H) / MOL", d2, mol, ":3435", "then MIN(., 1)")
     cm_q = site("CM = KARMAN**2 / CMFM**2", c(0.16), cmfm * cmfm, ":3499",
@@ -373,19 +460,20 @@ def main():
     # ---- ragrb (iter >= 2), :3301-3306 ----
     gt = site("GRAV / TAH", c(GRAV), tah, ":3313")
     tmp1g = site("TMP1 = KARMAN*(GRAV/TAH)*HG / RHOCP", KARMAN * gt * hg, rhocp, ":3313")
-    tmp1g = M(1e-6, tmp1g.hi)
-    molg = site("MOLG = -FV**3 / TMP1", fv3, tmp1g, ":3315")
+    tmp1g = M(1e-6, tmp1g.hi, False, ANY)
+    molg = site("MOLG = -FV**3 / TMP1", -fv3, tmp1g, ":3315")
     dzg = diff(zpd.nz(), z0)                        # ZPD - Z0MG, nonzero >= granularity
-    dzg = M(dzg.lo, D["HCAN_HI"] + D["Z0_HI"], True)
+    # (its zero: ZPD = Z0MG, a difference of equal nonzero floats, +0; ZPD = +0 gives -Z0MG)
+    dzg = M(dzg.lo, D["HCAN_HI"] + D["Z0_HI"], True).signed(diff(zpd, z0))
     mozg = site("MOZG = (ZPD-Z0MG) / MOLG", dzg, molg, ":3316", "then MIN(., 1)")
     fhg_lo = (1.0 + 15.0 * mozg.hi) ** -0.25        # (1 - 15 MOZG)**-0.25, MOZG < 0
     fhg = M(fhg_lo, 5.7)                            # 1 + 4.7 MOZG <= 5.7; averages stay inside
     sqrt_site("CWPC = SQRT(CWP*VAI*HCAN*FHG)", cwph * fhg, ":3343")
     cwpc = fn(math.sqrt, cwph * fhg)                # SQRT(CWP*VAI*HCAN*FHG)
     a14 = cwpc * z0
-    q14 = site("CWPC*Z0HG / HCAN", a14, hcan, ":3334", "Z0MG <= HCAN checked: <= CWPC")
+    q14 = site("-CWPC*Z0HG / HCAN", -a14, hcan, ":3334", "Z0MG <= HCAN checked: <= CWPC")
     q14 = M(q14.lo, cwpc.hi)
-    q15 = site("CWPC*(Z0H+ZPD) / HCAN", cwpc * z0, hcan, ":3335",
+    q15 = site("-CWPC*(Z0H+ZPD) / HCAN", -(cwpc * z0), hcan, ":3335",
                "Z0M + ZPD <= 2 HCAN checked: <= 2 CWPC")
     q15 = M(q15.lo, 2 * cwpc.hi)
     tmp1e = M(math.exp(-q14.hi), 1.0)
@@ -395,7 +483,7 @@ def main():
     # Z0MG <= Z0M + ZPD).  Nonzero, the difference is at least the granularity
     # of the smaller exponential; a negative RAHG fails the RAHG window below
     # and the lane re-runs with IEEE division.
-    dtmp = M(2.0 ** (math.floor(math.log2(tmp2e.lo)) - 23), 1.0, True)
+    dtmp = M(2.0 ** (math.floor(math.log2(tmp2e.lo)) - 23), 1.0, True).signed(diff(tmp1e, tmp2e))
     kh = M(1e-6, KARMAN * fv.hi * D["HCAN_HI"])    # MAX(KARMAN*FV*(HCAN-ZPD), MPE)
     site("RAHG = TMPRAH2 / KH", rah2a * dtmp, kh, ":3341", "then checked in [RAHG_LO, RAHG_HI]")
     den_rb = M(-math.expm1(-cwpc.lo / 2) * 0.999, -math.expm1(-cwpc.hi / 2))
@@ -418,20 +506,27 @@ def main():
     site("LAISHAE / (RB+RSSHA)", lai, rbrs, ":2828")
     # CTW = (1-FWET)*(...): its bound matters only through BEA's numerator
     # CEW + CTW, which is CTW = the two terms when FWET = 0 and >= CEW otherwise
-    ctw = M(t1.lo, 2 * t1.hi, True)
+    # 1 - FWET >= +0 (FWET <= 1; a zero difference is +0), times a sum of terms >= +0
+    one_m_fwet = M(2.0 ** -24, 1.0, True, POS, POS)
+    ctw = M(t1.lo, 2 * t1.hi, True).signed(one_m_fwet * (t1 + t1))
     cgw = site("CGW = 1 / (RAWG+RSURF)", c(1.0), M(rahg.lo, rahg.hi + rsurf_hi), ":2829")
     cond2 = cah + cew + ctw + cgw
     site("AEA = (EAIR*CAW + ESTG*CGW) / COND", M(es.lo * cgw.lo, eair_hi + es.hi * cgw.hi), cond2,
          ":2831")
-    bea = site("BEA = (CEW+CTW) / COND", M(min(cew.lo, ctw.lo), cew.hi + ctw.hi, True), cond2,
+    bea = site("BEA = (CEW+CTW) / COND",
+               M(min(cew.lo, ctw.lo), cew.hi + ctw.hi, True).signed(cew + ctw), cond2,
                ":2832", "FWET = 0: CTW = the LAI terms; FWET > 0: >= CEW")
-    one_m_bea = M(2.0 ** -24, 1.0, True)            # BEA <= 1; 1 - BEA is 0 or >= 2^-24
+    # BEA <= 1: COND = ((CAW + CEW) + CTW) + CGW >= CEW + CTW term by term (rounding
+    # is monotone), so 1 - BEA is +0 or >= 2^-24
+    one_m_bea = M(2.0 ** -24, 1.0, True, POS, POS)
     cev = site("CEV = (1-BEA)*CEW*RHOAIR*CPAIR / GAMMAV", one_m_bea * cew * rhocp, gammav, ":2833")
     # EAH = AEA + BEA*ESTV lies between 0 and max(EAIR, ESTG, ESTV); ESTV >= es.lo, so
     # ESTV - EAH is 0 or >= 2^(E - 23) with E the exponent of es.lo / 2
-    de = M(2.0 ** (math.floor(math.log2(es.lo / 2)) - 23), max(es.hi, eair_hi), True)
+    # (either sign: negative under dew; its zero is +0, ESTV > 0)
+    de = M(2.0 ** (math.floor(math.log2(es.lo / 2)) - 23), max(es.hi, eair_hi), True, ANY, POS)
+    # CEW = +0 (a dry canopy) times a negative ESTV - EAH is -0: keeps the fix-up
     site("EVC = FVEG*RHOAIR*CPAIR*CEW*(ESTV-EAH) / GAMMAV", fveg * rhocp * cew * de, gammav,
-         ":2842")
+         ":2842", "-0 under dew on a dry canopy", fix=True)
     eah = M(es.lo * cgw.lo / cond2.hi, max(es.hi, eair_hi))
     h_q = site("H = RHOAIR*CPAIR*(TAH-SFCTMP) / RAHC", rhocp * dT, rahc, ":2864")
     hg_q = site("HG = RHOAIR*CPAIR*(TG-TAH) / RAHG", rhocp * dT, rahg, ":2865")
@@ -445,14 +540,23 @@ def main():
     # (1-BTA)*RHOAIR*CPAIR*CVH <= RHOAIR*CPAIR*CVH; CTR <= RHOAIR*CPAIR*CTW / GAMMAV. ----
     numw = M(2.0 ** D["NUM_LO_EXP"] * (1 + 2 * W), 2.0 ** D["NUM_HI_EXP"], True)
     note = "numerator window checked per lane, IEEE loop outside"
-    site("CTR = (1-BEA)*CTW*RHOAIR*CPAIR / GAMMAV", numw, gammav, ":2834", note)
-    site("TR = FVEG*RHOAIR*CPAIR*CTW*(ESTV-EAH) / GAMMAV", numw, gammav, ":2843", note)
+    site("CTR = (1-BEA)*CTW*RHOAIR*CPAIR / GAMMAV", numw.signed(one_m_bea * ctw * rhocp), gammav,
+         ":2834", note)
+    # CTW = +0 (no transpiring leaf area, or FWET = 1) times a negative ESTV - EAH
+    site("TR = FVEG*RHOAIR*CPAIR*CTW*(ESTV-EAH) / GAMMAV", numw.signed(fveg * rhocp * ctw * de),
+         gammav, ":2843", note + "; -0 under dew", fix=True)
     emv = M(-math.expm1(-D["VAI_LO"] * D["FVEG_LO"]) * 0.9, 1.0)  # fp32 rounding of 1 - EXP(-x) near 1: < 6e-8
     cir = M(emv.lo * SB, 2 * SB)
     ctr_hi = rhocp.hi * ctw.hi / gammav.lo
     a_v = M(fveg.lo * 4 * cir.lo * T.lo ** 3,
             4 * cir.hi * T.hi ** 3 + rhocp.hi * cvh.hi + (cev.hi + ctr_hi) * des.hi)
-    site("DTV = B / A", numw, a_v, ":2852", note)
+    # B = SAV - IRC - SHC - EVC - TR: x - y is -0 only for x = -0, and SAV (SAG in
+    # the bare loop) = 0.0 + CAD + CAI starts from +0.0, so it is never -0
+    # whatever the signs of its terms; nor is any partial difference, nor B
+    sav = M(1e-30, 1e4, True, ANY, POS)
+    flux = M(1e-30, 1e4, True, ANY, ANY)
+    b_n = diff(diff(diff(diff(sav, flux), flux), flux), flux)
+    site("DTV = B / A", numw.signed(b_n), a_v, ":2852", note)
     # ---- bare_flux's Newton loop (:3120-3200; sflx_kernel.hip bare_loop) ----
     # Same sfcdif1 sites with Z0H = Z0MG and ZPD = ZPDG (the snow depth): the
     # kernel checks the same limits on TMPCM.., ZLVL-ZPDG, Z0MG, SFCTMP, air,
@@ -460,8 +564,9 @@ def main():
     # CSH*(TGB-SFCTMP) with CSH = RHOAIR*CPAIR/RAHB, RAHB in RAHC's interval, so
     # H has the canopy loop's interval and every sfcdif1 bound above carries over.
     rahb = rahc
-    hb = M((rhocp * dT).lo / rahb.hi, (rhocp * dT).hi, True)
+    hb = M((rhocp * dT).lo / rahb.hi, (rhocp * dT).hi, True).signed(rhocp * dT)  # CSH > 0
     assert hb.lo >= h.lo * 0.999 and hb.hi <= h.hi * 1.001
+    assert hb.sg <= h.sg and hb.zs <= h.zs
     site("bare: RAHB: 1 / (CH*UR)", c(1.0), cm * ur, ":3167", "then MAX(1, .)")
     site("bare: EHB = 1 / RAHB", c(1.0), rahb, ":3172")
     site("bare: CSH = RHOAIR*CPAIR / RAHB", rhocp, rahb, ":3186")
@@ -472,7 +577,7 @@ def main():
     # EMG in [0, 1] and CGH in [0, CGH_HI] checked per column): >= CSH
     a_b = M(rhocp.lo / rahb.hi,
             4 * SB * T.hi ** 3 + rhocp.hi / rahb.lo + cevb.hi * des.hi + D["CGH_HI"])
-    site("bare: DTG = B / A", numw, a_b, ":3198", note)
+    site("bare: DTG = B / A", numw.signed(b_n), a_b, ":3198", note)
 
     stomata_sites(D, T, p, es, rb)
     soil_sites()
@@ -481,16 +586,27 @@ def main():
     # ---- induction: the iteration ends inside the intervals it started from ----
     assert h_q.hi <= h.hi * 1.001 and h_q.lo >= h.lo * 0.999, (h_q, h)
     assert hg_q.hi <= hg.hi * 1.001 and hg_q.lo >= hg.lo * 0.999, (hg_q, hg)
+    assert h_q.sg <= h.sg and h_q.zs <= h.zs and hg_q.sg <= hg.sg and hg_q.zs <= hg.zs
     assert eah.hi <= max(es.hi, eair_hi) * 1.001
     assert p.lo - 0.378 * eah.hi > 0
 
-    print(f"domain: {HDR}")
+    print(f"domain: {os.path.relpath(HDR, ROOT)}")
     print(f"exact region: |b| in [2^-126, 2^126], a = 0 or |a| >= 2^-102, |a/b| in [2^-126, 2^126]; "
           f"sqrt: x finite and >= 2^-96")
-    print(f"{'site':46s} {'func.f90':8s} {'|a|':>22s} {'|b|':>22s} {'|a/b|':>22s}  ok")
-    for name, ref, a, b, q, ok, note in rows:
-        print(f"{name:46s} {ref:8s} {a!r:>22s} {b!r:>22s} {q!r:>22s}  {'yes' if ok else 'NO'}"
-              + (f"  ({note})" if note else ""))
+    print("fix-up: 'dropped' = declared fix-up-free (DivFast32::divn), needs a numerator that is "
+          "never -0; 'kept' = DivFast32::div")
+    print(f"{'site':46s} {'func.f90':8s} {'|a|':>22s} {'|b|':>22s} {'|a/b|':>22s}  ok   "
+          f"{'sign of a':10s} {'a = -0':7s} fix-up")
+    nofix = 0
+    for name, ref, a, b, q, ok, note, fix in rows:
+        if fix is None:      # a sqrt site
+            tail = ""
+        else:
+            nofix += not fix
+            tail = (f"  {sgn(a):10s} {'maybe' if a.neg0() else 'never':7s} "
+                    f"{'kept' if fix else 'dropped'}")
+        print(f"{name:46s} {ref:8s} {a!r:>22s} {b!r:>22s} {q!r:>22s}  {'yes' if ok else 'NO '}"
+              + tail + (f"  ({note})" if note else ""))
     print(f"derived: FHG >= {fhg_lo:.3g}, CWPC in {cwpc!r}, FV in {fv!r}, RAHC in {rahc!r}, "
           f"RB in {rb!r}")
     print("libm sites (in-range cores, csrc/glibc_math.h): expf |x| < 88; logf, powf x in "
@@ -506,6 +622,7 @@ def main():
         return 1
     print(f"all {len(libm_rows)} libm sites inside their cores' intervals")
     print(f"all {len(rows)} sites inside the exact region")
+    print(f"{nofix} sites fix-up-free, none with a numerator that can be -0")
     return 0
 
 

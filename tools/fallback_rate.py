@@ -6,6 +6,13 @@ through NOAHMP_ENGINE_LIB and steps the benchmark's column sets for the
 driver's window, printing re-runs per column-step.
 
     NOAHMP_ENGINE_LIB=$PWD/noahmp-1_amd/lib/variants/lib_fbcount.so python tools/fallback_rate.py
+
+The same build forms v_div_fixup_f32's result beside every fix-up-free
+quotient (DivFast32::divn) of a lane that keeps its loop and counts, per group
+of sites, the quotients formed and those whose bits the fix-up would have
+changed (counters 50..57; read and cleared after every step, since a million
+columns form more than 2^32 quotients over the window).  The second count must
+be 0 everywhere.
 """
 import os
 import sys
@@ -38,6 +45,7 @@ def main():
                  27: "TR numerator", 28: "DTV numerator", 29: "bare: DTG numerator",
                  30: "bare: EMG/CGH", 32: "libm: MOZ/MOZ2 window", 33: "libm: MOZG window",
                  34: "bare: libm MOZ/MOZ2 window"}
+    divn_groups = ("canopy loop + stomata", "bare loop", "soil sub-steps", "atanf_ge1")
     more = hasattr(raw, "nmp_debug_fallback_reasons")  # 64 counters (libm windows: 32..34)
     if more:
         raw.nmp_debug_fallback_reasons.argtypes = [C.c_void_p]
@@ -50,21 +58,33 @@ def main():
         cs = ColumnState.from_host(cols, "cuda:0")
         sh = StreamShards(eng, cs, 2)
         raw.nmp_debug_fallback_count(1, None)
+        why, fb = np.zeros(64, np.int64), 0
         for k in range(nsteps):
             jul = (180.0 + k * 1800.0 / 86400.0) % 366
             f = torch.as_tensor(cases.forcing_step(cols, jul, 366, k, seed=1000), device="cuda:0")
             sh.step(f, cases.CASE_NML_ZSOIL, 1800.0, jul, 366)
+            if more:  # per step: the divn counters would wrap over the window
+                sh.join()
+                torch.cuda.synchronize()
+                w = np.zeros(64, np.uint32)
+                raw.nmp_debug_fallback_reasons(w.ctypes.data)
+                fb += raw.nmp_debug_fallback_count(1, None)
+                why += w
         sh.join()
         torch.cuda.synchronize()
-        why = np.zeros(64, np.uint32)
-        if more:
-            raw.nmp_debug_fallback_reasons(why.ctypes.data)
-        fb = raw.nmp_debug_fallback_count(1, None if more else why.ctypes.data)
+        if not more:
+            w = np.zeros(64, np.uint32)
+            fb = raw.nmp_debug_fallback_count(1, w.ctypes.data)
+            why += w
         print(f"{kind:8s} {n:8d} columns x {nsteps} steps: {fb} IEEE loop re-runs (canopy + bare) "
               f"({fb / (n * nsteps):.2e} per column-step), status bits "
               f"{int((cs.status != 0).sum())}", flush=True)
-        print("   by condition:", {why_names.get(b, b): int(why[b]) for b in range(64) if why[b]},
+        print("   by condition:", {why_names.get(b, b): int(why[b]) for b in range(50) if why[b]},
               flush=True)
+        if more:
+            print("   divn quotients formed / fix-up would have changed the bits:",
+                  {g: f"{int(why[50 + 2 * i])} / {int(why[51 + 2 * i])}"
+                   for i, g in enumerate(divn_groups)}, flush=True)
         eng.close()
 
 

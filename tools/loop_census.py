@@ -14,10 +14,15 @@ steps; --kernel IfLb1ELb0ELi5E is its no-diagnostics copy, OS 1 | kNoDiag):
     python tools/loop_census.py [--asm FILE] [--kernel IfLb1ELb0ELi1E] [--tree DIR]
 
 A loop is a backward branch and the code it spans.  The canopy loops are the
-two loops of 500 to 3000 instructions that hold the loop's 30-odd
-v_div_fixup_f32 and its fp64 libm arithmetic (>= 10 v_fma_f64): the fast one
-has the fewest IEEE sequences (v_div_scale_f32), the DivRef one is the next
-such loop after it.  Counts are static:
+two loops of 500 to 3000 instructions that hold the loop's reciprocals
+(>= 15 v_rcp_f32: one per shared denominator, or one per IEEE sequence) and its
+fp64 libm arithmetic (>= 10 v_fma_f64): the fast one has the fewest IEEE
+sequences (v_div_scale_f32; none, in fact), the DivRef one is the next such
+loop after it.  (Until the short divisions dropped their fix-up the loops were
+found by their 30-odd v_div_fixup_f32; the fast loop now keeps two, EVC's and
+TR's.)  "short quotients" counts the sequence q = a*r; e = fma(-b, q, a);
+q' = fma(e, r, q) by its two fmas, "without fix-up" those of them whose q' no
+v_div_fixup_f32 reads: DivFast32::divn.  Counts are static:
 one pass over the loop body, every branch arm counted once.
 profiles/libm_inrange/loop_census.txt keeps the output for the parent and for
 this tree.
@@ -97,6 +102,49 @@ def classify(op):
     return "memory"
 
 
+def short_quotients(body):
+    """-> (short quotients, of them without a fix-up).  e = fma(-b, q, a) with a
+    not the constant 1.0 (that is the reciprocal's own Newton step), then
+    fma(e, r, q) -- as v_fma_f32 or the accumulating v_fmac_f32 -- before e or q
+    is written again; with a fix-up when a v_div_fixup_f32 reads that result
+    as its first source.  The IEEE sequence holds the same two fmas: there a
+    v_div_fmas_f32 reads the result, and the pair is not counted.  A pattern
+    count: a quotient whose registers the scheduler interleaves otherwise is
+    missed (29 of the fast loop's 34 are found)."""
+    fma = re.compile(r"v_fma_f32\s+(\S+), (\S+), (\S+), (\S+)$")
+    fmac = re.compile(r"v_fmac_f32(?:_e32|_e64)?\s+(\S+), (\S+), (\S+)$")
+    n = nofix = 0
+    for i, t in enumerate(body):
+        m = fma.match(t)
+        if not m or not m.group(2).startswith("-") or m.group(4) in ("1.0", "-1.0"):
+            continue
+        e, q = m.group(1), m.group(3)
+        for j in range(i + 1, min(i + 60, len(body))):
+            u = body[j]
+            m2, m3 = fma.match(u), fmac.match(u)
+            if (m2 and e in m2.group(2, 3) and m2.group(4) == q) or \
+                    (m3 and m3.group(1) == q and e in m3.group(2, 3)):
+                res = m2.group(1) if m2 else q
+                fixed = ieee = False
+                for k in range(j + 1, min(j + 60, len(body))):
+                    w = [x.rstrip(",") for x in body[k].split()]
+                    if w[0].startswith("v_div_fmas_f32") and res in w[2:]:
+                        ieee = True     # the IEEE sequence's own refinement step
+                        break
+                    if w[0].startswith("v_div_fixup_f32") and len(w) > 2 and w[2] == res:
+                        fixed = True
+                        break
+                    if len(w) > 1 and w[1] == res:
+                        break
+                n += not ieee
+                nofix += not ieee and not fixed
+                break
+            w = u.split()
+            if len(w) > 1 and w[1].rstrip(",") in (e, q):
+                break
+    return n, nofix
+
+
 def census(body):
     ops = Counter(opcode(t) for t in body)
     cls = Counter()
@@ -120,6 +168,8 @@ def census(body):
              ("v_div_fixup_f32", ops["v_div_fixup_f32"]),
              ("v_rcp_f32", ops["v_rcp_f32"]),
              ("v_fma_f64", ops["v_fma_f64"])]
+    sq, nofix = short_quotients(body)
+    rows += [("short quotients", sq), ("  without fix-up (divn)", nofix)]
     return rows
 
 
@@ -127,8 +177,7 @@ def canopy_loops(ins, labels):
     cand = []
     for a, b in loops(ins, labels).items():
         ops = Counter(opcode(t) for t in ins[a:b + 1])
-        if 500 <= b - a + 1 <= 3000 and 30 <= ops["v_div_fixup_f32"] <= 45 and \
-                ops["v_fma_f64"] >= 10:
+        if 500 <= b - a + 1 <= 3000 and ops["v_rcp_f32"] >= 15 and ops["v_fma_f64"] >= 10:
             cand.append((ops["v_div_scale_f32"], a, b))
     fast = min(cand, default=None)
     after = sorted(c[1:] for c in cand if fast and c[1] > fast[2])
