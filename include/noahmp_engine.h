@@ -35,6 +35,9 @@
  *   nmp_forcing_from_ldasin_interp  from the two resident blocks at the interval's ends
  * nmp_state_output            no counterpart: the soil, snow and canopy state of an output step as
  *                             output rows (the NMP_X_* groups), formed on the device
+ * nmp_state_drift,            no counterpart: a spin-up's convergence test -- the state's drift
+ *   nmp_drift_reduce          between two passes over the forcing period (the NMP_G_* groups)
+ *                             and its max / argmax / count / weighted sum, on the device
  * nmp_frh2o, nmp_frh2o_host   frh2o (public routine)       core/module_noahmp_func.f90:4494-4598
  * nmp_calhum, nmp_calhum_host calhum (public by default)     core/module_noahmp_func.f90:3958-3984
  * nmp_state_from_aos          layout bridge from noahmp_state_t records
@@ -672,6 +675,100 @@ enum {
 int nmp_state_output(nmp_engine* eng, int64_t ncol, int64_t ld, const void* state,
                      const int32_t* isnow, const int32_t* static_i, uint32_t groups,
                      double fill, void* out, int64_t ld_out, void* stream);
+
+/* Spin-up drift (no counterpart in the reference): a spin-up runs the forcing
+ * period over and over from the state the last pass left until the state at
+ * the end of a pass stops changing.  nmp_state_drift measures that change per
+ * column next to the state, nmp_drift_reduce reduces it to a few dozen
+ * numbers, so a loop's convergence test costs no copy of the state.
+ *
+ * Tracked values (NMP_K_*, NMP_NTRACKED = 13 rows, engine precision T), formed
+ * from the state block (NMP_S_* rows, leading dimension ld), ISNOW and the
+ * static integers.  Every operation is one IEEE operation, rounded once (no
+ * fused multiply-add), in the order stated, so a host given the same arrays
+ * reproduces every bit (noahmp-1_amd/spinup.py tracked_host, drift_host):
+ *   rows 0..3   SMC[i], i = 0..3, as stored
+ *   rows 4..7   STC[NMP_NSNOW + i], i = 0..3, as stored
+ *   row  8      SNEQV      row 9   WA      row 10   ZWT, as stored
+ *   row  11     TWS: the expression of nmp_water_storage, bit for bit:
+ *               ((CANLIQ + CANICE) + SNEQV) + WA, then for i = 1..4
+ *               + (SMC_i * dz_i) * 1000 in T, with zb = ZSNSO[i+2] and
+ *               dz_i = -zb where i == isnow + 1, else ZSNSO[i+1] - zb;
+ *               0 where IST != 1
+ *   row  12     CTOT = ((((LFMASS + RTMASS) + STMASS) + WOOD) + STBLCP) + FASTCP
+ * The kernel reads those state rows and no others: SMC, STC[3..6], SNEQV, WA,
+ * ZWT, ZSNSO[2..6], CANLIQ, CANICE and the six pools, plus ISNOW and IST.
+ *
+ * Drift groups (NMP_G_*, NMP_NDRIFT = 7 rows, T) against the snapshot `snap`
+ * of the tracked values an earlier call stored:
+ *   SNEQV, WA, ZWT, TWS, CARBON   fabs(now - snap) of rows 8, 9, 10, 11, 12:
+ *                                 one subtraction in T
+ *   SOIL_M (rows 0..3), SOIL_T (rows 4..7)   x_i = fabs(now_i - snap_i) of the
+ *                                 four layers; m = x_0, then for i = 1, 2, 3:
+ *                                 m = (x_i > m || x_i != x_i) ? x_i : m.  A NaN
+ *                                 sticks: once m is NaN no layer replaces it.
+ *
+ * nmp_state_drift, one lane per column: where drift is not NULL it writes the
+ * 7 drift rows (drift[g*ld_drift + c]) of the state against snap; then it
+ * stores the new tracked values into snap (snap[k*ld_snap + c]), so one call
+ * measures a loop and arms the next.  With drift NULL it only takes the
+ * snapshot (snap is not read).  Columns >= ncol and rows beyond those named
+ * are never touched.  Pointers may be offset by a range's first column, as for
+ * nmp_water_storage; one kernel enqueued on `stream`.  NMP_E_ARG, with nothing
+ * enqueued, for ld < ncol, ld_snap < ncol, ld_drift < ncol (with a drift), or a
+ * NULL state, isnow, static_i or snap; ncol == 0 is NMP_OK with nothing
+ * enqueued.
+ *
+ * nmp_drift_reduce reduces the 7 drift rows (T, drift[g*ld_drift + c]) of ncol
+ * columns -- one call for the rank's whole block.  weight (double[ncol], or
+ * NULL = 1 for every column) is the caller's mask and the mean's weight; tol
+ * is double[7].  Results, per group g:
+ *  - Skipped columns.  A column whose weight is exactly 0 is skipped in
+ *    everything below: it is not loaded.
+ *  - out_max[g]: the largest drift of the unskipped columns, converted exactly
+ *    to double; the quiet NaN 0x7ff8000000000000 if any unskipped column's
+ *    drift is NaN; +0.0 when no column is unskipped.
+ *  - out_arg[g] (int64): the lowest column index that holds a NaN if there is
+ *    one, otherwise the lowest index whose drift equals out_max[g]; -1 when no
+ *    column is unskipped.
+ *  - out_count[g] (int64): the number of unskipped columns with
+ *    !((double)d <= tol[g]); a NaN drift counts as not converged.
+ *  - out_wsum[g]: the weighted sum by a fixed tree.  One wavefront handles each
+ *    chunk of NMP_DRIFT_CHUNK = 256 columns, chunk k = columns
+ *    [256 k, 256 k + 256).  Lane l starts at x = +0.0 and for j = 0, 1, 2, 3 in
+ *    this order takes column c = 256 k + l + 64 j; unless c >= ncol or the
+ *    column is skipped: x = x + (double)d * w (one rounded product, then one
+ *    add; such a column is neither loaded nor multiplied).  Then, for s = 32,
+ *    16, 8, 4, 2, 1: x[l] = x[l] + x[l xor s] for every lane -- numpy's
+ *      for s in (32, 16, 8, 4, 2, 1): a = a[:s] + a[s:2*s]
+ *    and the chunk's partial is x[0].  Pass 2 adds the chunk partials in chunk
+ *    order from +0.0.
+ *  - *out_wtot: the weights summed by the same tree (x = x + w per column).
+ *    The weighted mean is out_wsum[g] / *out_wtot, formed by the caller.
+ * max, arg and count do not depend on the order of combination; the sum's tree
+ * depends on ncol alone, never on the launch shape, the stream or T's width.
+ * All arithmetic is IEEE double, each operation rounded once; no atomics.
+ * partial is caller scratch of NMP_DRIFT_SCRATCH * ceil(ncol / 256) 8-byte
+ * words.  Device pointers; two kernels enqueued on `stream` in order; the call
+ * neither synchronises nor allocates.  NMP_E_ARG for ld_drift < ncol or a NULL
+ * pointer other than weight; ncol == 0 is NMP_OK and writes the empty result
+ * (max, wsum, wtot +0.0, arg -1, count 0). */
+enum {
+  NMP_K_SMC = 0, NMP_K_STC = 4, NMP_K_SNEQV = 8, NMP_K_WA, NMP_K_ZWT, NMP_K_TWS, NMP_K_CTOT,
+  NMP_NTRACKED = 13
+};
+enum {
+  NMP_G_SOIL_M = 0, NMP_G_SOIL_T, NMP_G_SNEQV, NMP_G_WA, NMP_G_ZWT, NMP_G_TWS, NMP_G_CARBON,
+  NMP_NDRIFT = 7
+};
+enum { NMP_DRIFT_CHUNK = 256, NMP_DRIFT_SCRATCH = 29 };
+int nmp_state_drift(nmp_engine* eng, int64_t ncol, int64_t ld, const void* state,
+                    const int32_t* isnow, const int32_t* static_i, void* snap, int64_t ld_snap,
+                    void* drift /* may be NULL */, int64_t ld_drift, void* stream);
+int nmp_drift_reduce(nmp_engine* eng, int64_t ncol, int64_t ld_drift, const void* drift,
+                     const double* weight /* may be NULL */, const double* tol, void* partial,
+                     double* out_max, int64_t* out_arg, double* out_wsum, int64_t* out_count,
+                     double* out_wtot, void* stream);
 
 int nmp_run(nmp_engine* eng, int64_t ncol, int64_t ld, const float zsoil[4], float dt,
             float julian0, int32_t yearlen, int32_t nsteps, void* state, int32_t* isnow,

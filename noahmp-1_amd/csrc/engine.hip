@@ -525,6 +525,39 @@ int nmp_state_output(nmp_engine* eng, int64_t ncol, int64_t ld, const void* stat
              : NMP_E_DEVICE;
 }
 
+int nmp_state_drift(nmp_engine* eng, int64_t ncol, int64_t ld, const void* state,
+                    const int32_t* isnow, const int32_t* static_i, void* snap, int64_t ld_snap,
+                    void* drift, int64_t ld_drift, void* stream) {
+  if (!eng || ncol < 0 || ld < ncol || ld >= kMaxColumns || ld_snap < ncol ||
+      ld_snap >= kMaxColumns || (drift && (ld_drift < ncol || ld_drift >= kMaxColumns)))
+    return NMP_E_ARG;
+  if (ncol == 0) return NMP_OK;
+  if (!state || !isnow || !static_i || !snap) return NMP_E_ARG;
+  if (ensure_device(eng->device) != NMP_OK) return NMP_E_DEVICE;
+  std::lock_guard<std::mutex> lk(eng->host_mu);
+  return nmp::launch_state_drift(eng->precision, ncol, ld, state, isnow, static_i, snap, ld_snap,
+                                 drift, ld_drift, static_cast<hipStream_t>(stream)) == hipSuccess
+             ? NMP_OK
+             : NMP_E_DEVICE;
+}
+
+int nmp_drift_reduce(nmp_engine* eng, int64_t ncol, int64_t ld_drift, const void* drift,
+                     const double* weight, const double* tol, void* partial, double* out_max,
+                     int64_t* out_arg, double* out_wsum, int64_t* out_count, double* out_wtot,
+                     void* stream) {
+  if (!eng || ncol < 0 || ld_drift < ncol || ld_drift >= kMaxColumns) return NMP_E_ARG;
+  if (!drift || !tol || !partial || !out_max || !out_arg || !out_wsum || !out_count || !out_wtot)
+    return NMP_E_ARG;
+  if (ensure_device(eng->device) != NMP_OK) return NMP_E_DEVICE;
+  // the two passes of one call are enqueued back to back
+  std::lock_guard<std::mutex> lk(eng->host_mu);
+  return nmp::launch_drift_reduce(eng->precision, ncol, ld_drift, drift, weight, tol, partial,
+                                  out_max, out_arg, out_wsum, out_count, out_wtot,
+                                  static_cast<hipStream_t>(stream)) == hipSuccess
+             ? NMP_OK
+             : NMP_E_DEVICE;
+}
+
 int nmp_forcing_from_ldasin_geo(nmp_engine* eng, int64_t ncol, int64_t ld, const float* ldasin,
                                 const double* geo, double sin_decl, double cos_decl, double ha0,
                                 void* forcing, void* stream) {

@@ -107,6 +107,18 @@ hipError_t launch_state_output(int precision, const DevParams* P, int64_t ncol, 
                                uint32_t groups, double fill, void* out, int64_t ld_out,
                                hipStream_t stream);
 
+// csrc/drift.hip: a spin-up's convergence test -- the 7 NMP_G_* drift rows of
+// the state against the snapshot of its 13 tracked values (drift may be null:
+// snapshot only), which then takes the new values; and the rows' reduction
+// (pass 1: chunk partials, pass 2: the results), both enqueued on `stream`
+hipError_t launch_state_drift(int precision, int64_t ncol, int64_t ld, const void* state,
+                              const int32_t* isnow, const int32_t* static_i, void* snap,
+                              int64_t ld_snap, void* drift, int64_t ld_drift, hipStream_t stream);
+hipError_t launch_drift_reduce(int precision, int64_t ncol, int64_t ld_drift, const void* drift,
+                               const double* weight, const double* tol, void* partial,
+                               double* out_max, int64_t* out_arg, double* out_wsum,
+                               int64_t* out_count, double* out_wtot, hipStream_t stream);
+
 // csrc/routines.hip: the reference's public routines frh2o / calhum over n
 // elements (device pointers, engine precision; math 0 = the fp32 "ref" policy)
 hipError_t launch_frh2o(int precision, int math, const DevParams* P, int64_t n,

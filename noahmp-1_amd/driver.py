@@ -226,6 +226,12 @@ class OfflineDriver:
         self.zsoil = [float(z) for z in zsoil]
         self.dt = cfg.timestep.total_seconds()
         self.t, self.step_index, self.write = cfg.begdatetime, 0, write
+        # spin-up: where the run stands before its first step, the shard's place
+        # among the ranks' columns, and the columns' latitudes (the mean's weights)
+        self._start, self._first_col, self._total = (self.t, self.step_index), first, total
+        self._lat = np.asarray(cols.static_f[L.STATIC_F.index("LAT")], np.float64)
+        self.spinup_history, self.spinup_stop = [], None
+        self._spin = None
         self.accumulate = bool(accumulate)
         self.out_names = L.DIAG_OUT_ACC if self.accumulate else L.DIAG_OUT
         self.nflux, region_rows = len(self.out_names), None
@@ -328,6 +334,7 @@ class OfflineDriver:
         drv = cls(cfg, cols, device, P, forcing, grid=grid, regions=regions,
                   region_weights=region_weights, **kw)
         drv.t, drv.step_index = t0, step
+        drv._start = (t0, step)
         drv.perm, drv.cols_index, drv.output.perm = perm, idx, perm
         if drv.accumulate:
             a = ncio.read_accum(init or cfg.initfile, grid)
@@ -389,6 +396,7 @@ class OfflineDriver:
             self.cs.isnow.copy_(torch.as_tensor(np.ascontiguousarray(isn[idx]), device=self.dev))
             if self.accum is not None:
                 self.accum.restore(ncio.read_accum(path, self.grid), idx)
+            self._start = (self.t, self.step_index)
             return
         with np.load(path, allow_pickle=False) as z:
             assert str(z["layout"]) == ",".join(n for n, _ in L.STATE_FIELDS), "state layout"
@@ -400,6 +408,7 @@ class OfflineDriver:
             if self.accum is not None:
                 self.accum.restore((z["acc"], z["stor_beg"], int(z["acc_steps"]))
                                    if "acc" in z.files else None)
+        self._start = (self.t, self.step_index)
 
     # ---- time loop -----------------------------------------------------------------
     # the interpreter's thread switch interval while the loop runs: the file
@@ -512,3 +521,161 @@ class OfflineDriver:
         """Wait until every output file issued so far is written (raises a
         writer's error)."""
         self.output.flush()
+
+    # ---- spin-up -------------------------------------------------------------------
+    def spinup(self, loops: int, tol=None, min_loops: int = 1, report: bool = True,
+               drift_map: bool = False):
+        """Bring the state to equilibrium with the forcing: run from where the
+        driver stands to cfg.enddatetime up to `loops` times, each pass from
+        the state the pass before left, writing nothing, and measure on the
+        device how far the state at the end of each pass lies from the end of
+        the pass before (nmp_state_drift per column range, nmp_drift_reduce
+        once over the rank's block; spinup.py states both in numpy).  Only
+        while the driver stands at the time it was constructed or loaded for
+        (RuntimeError otherwise); after every pass, the last included, time
+        and step index go back there, the feed forgets its resident blocks and
+        an accumulating run starts a fresh interval from the spun-up state.
+        The state, ISNOW and the status bits stay: `run()` afterwards is the
+        production run from the spun-up state.
+
+        tol: the groups' tolerances (spinup.parse_tol: "SOIL_M=0.001,SOIL_T=
+        0.01", a dict or 7 numbers; a group not named never holds the loop up).
+        The loop ends early once at least min_loops passes have run and no
+        column's drift exceeds its group's tolerance.  None: every pass runs
+        and the drift is only reported.  There are no default tolerances.
+        Each pass appends a spinup.SpinupRecord to `spinup_history` (per group
+        the largest drift, its global column, the weighted mean, the count of
+        columns over the tolerance); `spinup_stop` says why the loop ended.
+        The mean's weights are cos(latitude) of the columns in double
+        (regions.area_weights), 1 where the latitudes are not finite.
+
+        Under a process group every rank reduces its shard; the largest
+        drift, its column as a global index and the count are combined
+        exactly, so they and the stop decision are the same at any world
+        size.  The mean adds the ranks' weighted sums and weights in rank
+        order on the host: its last bits depend on the world size.
+
+        report: rank 0 writes <outdir>/SPINUP.json (history, groups, units,
+        tolerances, stop reason).  drift_map (a run on a grid, single rank):
+        the last pass's 7 drift rows on the grid as
+        <outdir>/SPINUP_DRIFT_DOMAIN1, variables DRIFT_<GROUP>."""
+        from . import spinup as sp
+        loops, min_loops = int(loops), int(min_loops)
+        if loops < 1 or min_loops < 1:
+            raise ValueError("spinup: loops and min_loops must be at least 1")
+        if drift_map and (self.grid is None or dist.is_initialized()):
+            raise ValueError("spinup: drift_map needs a run on a grid, on a single rank")
+        if (self.t, self.step_index) != self._start:
+            raise RuntimeError("spinup: the run has moved on from the time it was constructed "
+                               f"or loaded for ({self._start[0].isoformat()})")
+        if self.t >= self.cfg.enddatetime:
+            raise ValueError("spinup: no step lies between the start and enddatetime")
+        tol_arr = np.full(L.NDRIFT, np.inf) if tol is None else sp.parse_tol(tol)
+        n = self.cs.ncol
+        if self._spin is None:
+            w = area_weights(self._lat) if np.isfinite(self._lat).all() else np.ones(n)
+            self._spin = dict(
+                weight=torch.as_tensor(np.ascontiguousarray(w, np.float64), device=self.dev),
+                snap=torch.zeros((L.NTRACKED, n), dtype=self.dtype, device=self.dev),
+                drift=torch.zeros((L.NDRIFT, n), dtype=self.dtype, device=self.dev))
+        snap, drift, weight = self._spin["snap"], self._spin["drift"], self._spin["weight"]
+        self._drift_pass(snap, None)
+        write, self.write = self.write, False   # no LDASOUT, REGIONS or RESTART file
+        self.spinup_stop = f"ran all {loops} loops"
+        try:
+            for k in range(1, loops + 1):
+                self.run()
+                self._drift_pass(snap, drift)
+                res = self.engine.drift_reduce(drift, tol_arr, weight)
+                rec = self._spinup_record(k, res, tol_arr)
+                self.spinup_history.append(rec)
+                self._rewind()
+                if tol is not None and k >= min_loops and rec.converged:
+                    self.spinup_stop = f"converged after loop {k}"
+                    break
+        finally:
+            self.write = write
+        rank0 = not dist.is_initialized() or dist.get_rank() == 0
+        if report and rank0:
+            import json
+            os.makedirs(self.cfg.outdir, exist_ok=True)
+            with open(os.path.join(self.cfg.outdir, "SPINUP.json"), "w") as f:
+                json.dump({"groups": list(L.DRIFT_GROUPS),
+                           "units": [L.DRIFT_UNITS[g] for g in L.DRIFT_GROUPS],
+                           "tol": sp.SpinupRecord(0, tol=tol_arr.tolist()).as_json()["tol"],
+                           "min_loops": min_loops, "loops": loops, "stop": self.spinup_stop,
+                           "start": self._start[0].isoformat(),
+                           "end": self.cfg.enddatetime.isoformat(),
+                           "history": [r.as_json() for r in self.spinup_history]}, f, indent=1)
+        if drift_map:
+            self._write_drift_map(drift)
+        return self
+
+    def _drift_pass(self, snap: torch.Tensor, drift):
+        """nmp_state_drift for every column range on its stream, after the
+        caller's stream; then the caller's stream waits for the ranges."""
+        cur = torch.cuda.current_stream(self.dev)
+        for st, rng in zip(self.ranges.streams, self.ranges.ranges):
+            st.wait_stream(cur)
+            self.engine.state_drift(self.cs, snap, drift, stream=st, cols=rng)
+        self.ranges.join()
+
+    def _rewind(self):
+        """Back to the run's start with the state as it is."""
+        self.ranges.join()
+        self.t, self.step_index = self._start
+        self.feed.reset()   # resident blocks and read-ahead belong to the old time
+        if self.accum is not None:
+            self.accum.restore(None)
+
+    def _spinup_record(self, k: int, res, tol_arr):
+        """The loop's record from this rank's reduction; under a process group
+        from every rank's, combined as spinup() documents."""
+        from . import spinup as sp
+        mx, arg, count = res.max.copy(), res.arg.copy(), res.count.copy()
+        arg[arg >= 0] += self._first_col
+        wsum, wtot = res.wsum.copy(), np.float64(res.wtot)
+        if dist.is_initialized():
+            on_host = dist.get_backend() == "gloo"
+            words = np.concatenate([mx.view(np.int64), arg, wsum.view(np.int64), count,
+                                    np.array([wtot]).view(np.int64)])
+            mine = torch.as_tensor(words, device="cpu" if on_host else self.dev)
+            every = [torch.empty_like(mine) for _ in range(dist.get_world_size())]
+            dist.all_gather(every, mine)
+            g = L.NDRIFT
+            parts = [e.cpu().numpy() for e in every]
+            mx, arg = np.zeros(g), np.full(g, -1, np.int64)
+            count, wsum, wtot = np.zeros(g, np.int64), np.zeros(g), np.float64(0.0)
+            for p in parts:                         # rank order
+                pm, pa = p[:g].view(np.float64), p[g:2 * g]
+                for i in range(g):
+                    if pa[i] < 0:
+                        continue
+                    n1, n2 = np.isnan(mx[i]), np.isnan(pm[i])
+                    if arg[i] < 0 or (n2 and not n1) or (not n1 and not n2 and pm[i] > mx[i]) \
+                            or (n1 == n2 and (n1 or pm[i] == mx[i]) and pa[i] < arg[i]):
+                        mx[i], arg[i] = pm[i], pa[i]
+                count = count + p[3 * g:4 * g]
+                wsum = wsum + p[2 * g:3 * g].view(np.float64)
+                wtot = wtot + p[4 * g:].view(np.float64)[0]
+        with np.errstate(all="ignore"):
+            mean = wsum / wtot
+        return sp.SpinupRecord(k, mx.tolist(), [int(a) for a in arg], mean.tolist(),
+                               [int(c) for c in count], tol_arr.tolist())
+
+    def _write_drift_map(self, drift: torch.Tensor):
+        """The drift rows on the grid (nmp_ldasout_grid) under the LDASOUT
+        header, stamped with the run's start time."""
+        idx = np.asarray(self.grid.index)
+        point = torch.as_tensor((idx if self.perm is None else idx[self.perm]).astype(np.int32),
+                                device=self.dev)
+        npts = self.grid.shape[0] * self.grid.shape[1]
+        f32 = self.dtype == torch.float32
+        out = torch.empty((L.NDRIFT, npts), device=self.dev,
+                          dtype=torch.int32 if f32 else torch.int64)
+        self.engine.ldasout_grid(drift, point, out, float(ncio.FILL))
+        a = out.cpu().numpy()
+        os.makedirs(self.cfg.outdir, exist_ok=True)
+        ncio.write_ldasout_grids(os.path.join(self.cfg.outdir, "SPINUP_DRIFT_DOMAIN1"), self.grid,
+                                 a.view(">f4" if f32 else ">f8"), self._start[0],
+                                 [f"DRIFT_{g}" for g in L.DRIFT_GROUPS])

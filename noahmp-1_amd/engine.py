@@ -461,6 +461,85 @@ class Engine:
                                               int(groups), float(fill), _ptr(out_rows, lo), n,
                                               C.c_void_p(s.cuda_stream)), "nmp_state_output")
 
+    # ---- spin-up drift (nmp_state_drift / nmp_drift_reduce) --------------------
+    def state_drift(self, cs: ColumnState, snap: torch.Tensor, drift: torch.Tensor | None = None,
+                    stream=None, cols: tuple[int, int] | None = None):
+        """nmp_state_drift: with `drift` (NDRIFT, n), the drift rows
+        (layout.DRIFT_GROUPS) of the state's tracked values against the
+        snapshot `snap` (NTRACKED, n); then `snap` takes the new tracked
+        values (layout.TRACKED).  drift=None only takes the snapshot.  Engine
+        precision; spinup.tracked_host / drift_host are the numpy form.
+        cols=(lo, hi) handles only those columns, enqueued on `stream`."""
+        n = cs.ncol
+        lo, hi = self._cols_range(n, cols)
+        self._check_block(cs.state, (L.NSTATE, n), self.dtype, "state")
+        self._check_block(cs.isnow, (n,), torch.int32, "isnow")
+        self._check_block(cs.static_i, (L.NSTATIC_I, n), torch.int32, "static_i")
+        self._check_block(snap, (L.NTRACKED, n), self.dtype, "snap")
+        if drift is not None:
+            self._check_block(drift, (L.NDRIFT, n), self.dtype, "drift")
+        s = stream if stream is not None else torch.cuda.current_stream(self.device)
+        _lib.check(self._lib.nmp_state_drift(self._h, hi - lo, n, _ptr(cs.state, lo),
+                                             _ptr(cs.isnow, lo), _ptr(cs.static_i, lo),
+                                             _ptr(snap, lo), n,
+                                             _ptr(drift, lo) if drift is not None else None, n,
+                                             C.c_void_p(s.cuda_stream)), "nmp_state_drift")
+
+    def drift_reduce(self, drift: torch.Tensor, tol, weight: torch.Tensor | None = None,
+                     stream=None):
+        """nmp_drift_reduce: per drift group the largest drift of the (NDRIFT,
+        n) block `drift` (engine precision) and its column, the count of
+        columns with !(d <= tol) and the weighted sum by the fixed tree
+        (spinup.reduce_host is the numpy form); tol: 7 numbers; weight: (n,)
+        float64 on the device or None (= 1), a column of weight 0 is skipped.
+        Returns a spinup.DriftResult (`max`, `arg`, `mean`, `count`, `wsum`,
+        `wtot`).  Enqueued on `stream`; the 29 result words are then copied to
+        the host, which waits for them.  The scratch and the result buffers
+        live with the engine, one set per column count, so calls of one size
+        must be ordered by their streams."""
+        from . import spinup
+        n = int(drift.shape[1]) if drift.dim() == 2 else -1
+        self._check_block(drift, (L.NDRIFT, n), self.dtype, "drift")
+        if weight is not None:
+            self._check_block(weight, (n,), torch.float64, "weight")
+        tol = np.ascontiguousarray(tol, np.float64)
+        assert tol.shape == (L.NDRIFT,), tol.shape
+        buf = self._drift_bufs(n)
+        s = stream if stream is not None else torch.cuda.current_stream(self.device)
+        res, w = buf["res"], buf["words"]
+        with torch.cuda.stream(s):
+            buf["tol_host"].copy_(torch.from_numpy(tol))
+            buf["tol"].copy_(buf["tol_host"], non_blocking=True)
+            _lib.check(self._lib.nmp_drift_reduce(
+                self._h, n, n, _ptr(drift), _ptr(weight), _ptr(buf["tol"]), _ptr(buf["partial"]),
+                _ptr(w, 0), _ptr(w, L.NDRIFT), _ptr(w, 2 * L.NDRIFT), _ptr(w, 3 * L.NDRIFT),
+                _ptr(w, 4 * L.NDRIFT), C.c_void_p(s.cuda_stream)), "nmp_drift_reduce")
+            res.copy_(w, non_blocking=True)
+            ev = torch.cuda.Event()
+            ev.record(s)
+        ev.synchronize()
+        h = res.numpy().copy()
+        g = L.NDRIFT
+        return spinup.DriftResult(h[:g].view(np.float64), h[g:2 * g], h[2 * g:3 * g].view(np.float64),
+                                  h[3 * g:4 * g], float(h[4 * g:].view(np.float64)[0]))
+
+    def _drift_bufs(self, n: int) -> dict:
+        """drift_reduce's buffers for n columns, allocated once per engine and
+        column count: the pass-1 scratch, the tolerances, and the result words
+        [max 7 | arg 7 | wsum 7 | count 7 | wtot] on the device and pinned."""
+        bufs = self.__dict__.setdefault("_drift_buf", {})
+        b = bufs.get(n)
+        if b is None:
+            dev = torch.device("cuda", self.device)
+            nchunk = max(-(-n // L.DRIFT_CHUNK), 1)
+            b = bufs[n] = dict(
+                partial=torch.empty(L.DRIFT_SCRATCH * nchunk, dtype=torch.int64, device=dev),
+                tol=torch.empty(L.NDRIFT, dtype=torch.float64, device=dev),
+                tol_host=torch.empty(L.NDRIFT, dtype=torch.float64, pin_memory=True),
+                words=torch.zeros(4 * L.NDRIFT + 1, dtype=torch.int64, device=dev),
+                res=torch.empty(4 * L.NDRIFT + 1, dtype=torch.int64, pin_memory=True))
+        return b
+
     # ---- region-aggregated output (nmp_region_reduce) ---------------------------
     def region_reduce(self, fields: torch.Tensor, plan, sums: torch.Tensor,
                       means: torch.Tensor | None = None, stream=None):

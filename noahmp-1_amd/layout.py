@@ -66,6 +66,19 @@ assert NXGROUP == 21 and NXROWS_NOFILL == 32 and NXROWS == 39
 # the six 2-D variables of the CARBON group, in row order
 CARBON_POOLS = ["LFMASS", "RTMASS", "STMASS", "WOOD", "STBLCP", "FASTCP"]
 
+# spin-up drift (nmp_state_drift / nmp_drift_reduce): the tracked values'
+# rows (NMP_K_*: name -> first row) and the drift groups (NMP_G_*) with the
+# units of their drift
+TRACKED = {"SMC": 0, "STC": 4, "SNEQV": 8, "WA": 9, "ZWT": 10, "TWS": 11, "CTOT": 12}
+NTRACKED = 13
+DRIFT_GROUPS = ["SOIL_M", "SOIL_T", "SNEQV", "WA", "ZWT", "TWS", "CARBON"]
+DRIFT_UNITS = {"SOIL_M": "m3 m-3", "SOIL_T": "K", "SNEQV": "mm", "WA": "mm", "ZWT": "m",
+               "TWS": "mm", "CARBON": "g m-2"}
+NDRIFT = len(DRIFT_GROUPS)
+DRIFT_CHUNK = 256     # columns per chunk of the reduction's tree (NMP_DRIFT_CHUNK)
+DRIFT_SCRATCH = 29    # 8-byte words of pass-1 scratch per chunk (NMP_DRIFT_SCRATCH)
+assert NDRIFT == 7
+
 # status bits (NMP_ST_*)
 ST_ERRSW, ST_ERRENG, ST_FIRE, ST_HCAN, ST_ZLVL, ST_FLERCH, ST_OPTVEG, ST_STOP = (
     1, 2, 4, 8, 16, 32, 64, 128)

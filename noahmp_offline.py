@@ -39,6 +39,26 @@ from noahmp_amd.params import Params  # noqa: E402
 DEFAULT_NAMELIST_FILE = "case.nml"
 
 
+def _spinup(drv, cfg, a):
+    """--spinup-loops: the spin-up before the production run, one line per loop."""
+    from noahmp_amd import layout
+    t0 = time.perf_counter()
+    drv.spinup(a.spinup_loops, tol=a.spinup_tol, min_loops=a.spinup_min_loops or 1,
+               drift_map=a.spinup_map)
+    el = time.perf_counter() - t0
+    for r in drv.spinup_history:
+        print(f"spin-up loop {r.loop}: " + "  ".join(
+            f"{g} max {m:.6g} ({c} over)" for g, m, c in zip(layout.DRIFT_GROUPS, r.max, r.count)))
+    print(f"spin-up: {drv.spinup_stop} in {el:.2f} s")
+    if a.spinup_restart:
+        os.makedirs(cfg.resdir, exist_ok=True)
+        stamp = drv.t.strftime("%Y%m%d%H")
+        path = os.path.join(cfg.resdir, f"RESTART.{stamp}_DOMAIN1.spinup" +
+                            (".nc" if drv.grid is not None else ".npz"))
+        drv.save_restart(path)
+        print(f"spin-up: state written to {path}")
+
+
 def main(argv=None):
     ap = argparse.ArgumentParser(description="Noah-MP Land Surface Model (MI355X engine)")
     ap.add_argument("nmlfile", nargs="?", default=DEFAULT_NAMELIST_FILE, help="configuration file")
@@ -101,7 +121,36 @@ def main(argv=None):
     ap.add_argument("--cosz-floor", type=float, default=0.05, metavar="X",
                     help="with --interp-sw zenith: lower bound of COSZ in the clearness ratio "
                          "SWDOWN / max(COSZ, X) (default 0.05)")
+    ap.add_argument("--spinup-loops", type=int, default=None, metavar="N",
+                    help="before the run, spin the state up: run the period up to N times, "
+                         "each pass from the state the pass before left, writing no output, "
+                         "and report the state's drift between passes (measured on the device)")
+    ap.add_argument("--spinup-tol", default=None, metavar="G=X[,G=X]",
+                    help="with --spinup-loops: stop once no column's drift exceeds these "
+                         "tolerances (groups SOIL_M, SOIL_T, SNEQV, WA, ZWT, TWS, CARBON; a "
+                         "group not named never holds the loop up)")
+    ap.add_argument("--spinup-min-loops", type=int, default=None, metavar="M",
+                    help="with --spinup-tol: run at least M passes (default 1)")
+    ap.add_argument("--spinup-map", action="store_true",
+                    help="netCDF cases: write the last pass's drift on the grid "
+                         "(SPINUP_DRIFT_DOMAIN1)")
+    ap.add_argument("--spinup-restart", action="store_true",
+                    help="write the spun-up state at the start time as a restart file "
+                         "(RESTART.<stamp>_DOMAIN1.spinup.nc, or .npz without a grid)")
     a = ap.parse_args(argv)
+    if a.spinup_loops is None and (a.spinup_tol is not None or a.spinup_min_loops is not None
+                                   or a.spinup_map or a.spinup_restart):
+        ap.error("--spinup-tol, --spinup-min-loops, --spinup-map and --spinup-restart need "
+                 "--spinup-loops")
+    if a.spinup_loops is not None:
+        from noahmp_amd import spinup
+        if a.spinup_loops < 1 or (a.spinup_min_loops is not None and a.spinup_min_loops < 1):
+            ap.error("--spinup-loops and --spinup-min-loops must be at least 1")
+        if a.spinup_tol is not None:
+            try:
+                spinup.parse_tol(a.spinup_tol)
+            except ValueError as e:
+                ap.error(str(e))
     if a.regions_only and not a.regions:
         ap.error("--regions-only needs --regions")
     if (a.downscale or a.nearest) and not a.forcing_grid:
@@ -147,6 +196,10 @@ def main(argv=None):
                                    precision=a.precision, accumulate=a.accumulate, **skw)
         if a.restart:
             drv.load_restart(a.restart)
+    if a.spinup_loops is not None:
+        if a.spinup_map and drv.grid is None:
+            ap.error("--spinup-map needs a run from files (a grid)")
+        _spinup(drv, cfg, a)
     t0 = time.perf_counter()
     drv.run()
     el = time.perf_counter() - t0

@@ -27,6 +27,12 @@ achieved HBM bandwidth against their algorithmic bytes, at 1,048,576 columns.
                            rows (192 B fp32), writes 39 rows (156 B); SOIL_M
                            alone: reads 4 rows, writes 4
                            (stateout.algorithmic_bytes)
+  state_drift              reads 24 state rows, ISNOW, IST and the 13-row
+                           snapshot, writes 7 drift rows and the snapshot
+                           (236 B fp32, 464 B fp64); the snapshot alone: reads
+                           the state rows, writes 13
+  drift_reduce             both passes: reads 7 drift rows and the weight
+                           (36 B fp32, 64 B fp64) (spinup.algorithmic_bytes)
 
 The two gather/scatter kernels are timed with the grid points in the
 columns' own order (`point` = identity: coalesced) and fully shuffled (every
@@ -36,7 +42,7 @@ between, mostly runs of neighbouring points).  Times are HIP events around
 `rocprofv3 --kernel-trace --stats` for the kernels' own durations.  Prints
 one JSON line per kernel, precision and point order.
 
-    python tools/io_kernels_bench.py [--ncol 1048576] [--reps 50]
+    python tools/io_kernels_bench.py [--ncol 1048576] [--reps 50] [--kernels NAME[,NAME]]
 """
 import argparse
 import json
@@ -50,7 +56,7 @@ import numpy as np  # noqa: E402
 import torch  # noqa: E402
 
 import noahmp_pkg  # noqa: E402,F401
-from noahmp_amd import cases as cases_mod, layout as L, stateout, timeman  # noqa: E402
+from noahmp_amd import cases as cases_mod, layout as L, spinup, stateout, timeman  # noqa: E402
 from noahmp_amd.engine import ColumnState, Engine  # noqa: E402
 from noahmp_amd.params import Params  # noqa: E402
 
@@ -70,12 +76,30 @@ def timed(fn, reps):
     return a.elapsed_time(b) / reps
 
 
+def _drift_reduce_args(eng, drift, weight, tol):
+    """nmp_drift_reduce's arguments with the engine's own buffers
+    (Engine.drift_reduce also copies the result to the host and waits for it:
+    timed here are the two launches alone)."""
+    import ctypes as C
+    from noahmp_amd.engine import _ptr
+    n, g = int(drift.shape[1]), L.NDRIFT
+    buf = eng._drift_bufs(n)
+    buf["tol"].copy_(torch.as_tensor(tol, device=drift.device))
+    w = buf["words"]
+    return (eng._h, n, n, _ptr(drift), _ptr(weight), _ptr(buf["tol"]), _ptr(buf["partial"]),
+            _ptr(w, 0), _ptr(w, g), _ptr(w, 2 * g), _ptr(w, 3 * g), _ptr(w, 4 * g),
+            C.c_void_p(torch.cuda.current_stream().cuda_stream))
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--ncol", type=int, default=1 << 20)
     ap.add_argument("--reps", type=int, default=50)
     ap.add_argument("--out", default=None, help="also write the results as one JSON list")
+    ap.add_argument("--kernels", default=None, metavar="NAME[,NAME]",
+                    help="time only these kernels (default: all)")
     a = ap.parse_args()
+    only = set(a.kernels.split(",")) if a.kernels else None
     n, dev = a.ncol, "cuda:0"
     rng = np.random.default_rng(0)
     npts = n
@@ -160,7 +184,25 @@ def main():
                           lambda mask=mask, nrow=nrow: eng.state_output(so_cs[prec], mask,
                                                                         so_out[:nrow], -9999.0),
                           n * stateout.algorithmic_bytes(mask, prec)))
+        # spin-up drift: the per-column kernel measuring a loop and arming the
+        # next (and taking the snapshot alone), and the reduction with weights
+        sp_bytes = spinup.algorithmic_bytes(prec)
+        sp_snap = torch.zeros((L.NTRACKED, n), dtype=dt, device=dev)
+        sp_drift = torch.as_tensor(rng.random((L.NDRIFT, n)), device=dev).to(dt)
+        sp_w = torch.as_tensor(np.cos(lat), device=dev)
+        sp_tol = np.full(L.NDRIFT, 0.5)
+        cases += [("state_drift", "drift + snapshot",
+                   lambda: eng.state_drift(so_cs[prec], sp_snap, sp_drift),
+                   n * sp_bytes["state_drift"]),
+                  ("state_drift", "snapshot only",
+                   lambda: eng.state_drift(so_cs[prec], sp_snap),
+                   n * sp_bytes["state_drift_snapshot"])]
+        dr_args = _drift_reduce_args(eng, sp_drift, sp_w, sp_tol)
+        cases.append(("drift_reduce", "weights, both passes",
+                      lambda: eng._lib.nmp_drift_reduce(*dr_args), n * sp_bytes["drift_reduce"]))
         for name, order, fn, nbytes in cases:
+            if only and name not in only:
+                continue
             ms = timed(fn, a.reps)
             gbs = nbytes / (ms * 1e-3) / 1e9
             r = {"kernel": name, "precision": prec, "ncol": n, "point_order": order,
