@@ -38,6 +38,9 @@
  * nmp_state_drift,            no counterpart: a spin-up's convergence test -- the state's drift
  *   nmp_drift_reduce          between two passes over the forcing period (the NMP_G_* groups)
  *                             and its max / argmax / count / weighted sum, on the device
+ * nmp_static_monthly          no counterpart: the vegetation fraction SHDFAC of a date from the
+ *                             12-month GREENFRAC climatology (fveg = SHDFAC with opt_veg = 1,
+ *                             core/module_noahmp_func.f90:366-368), on the device
  * nmp_frh2o, nmp_frh2o_host   frh2o (public routine)       core/module_noahmp_func.f90:4494-4598
  * nmp_calhum, nmp_calhum_host calhum (public by default)     core/module_noahmp_func.f90:3958-3984
  * nmp_state_from_aos          layout bridge from noahmp_state_t records
@@ -769,6 +772,38 @@ int nmp_drift_reduce(nmp_engine* eng, int64_t ncol, int64_t ld_drift, const void
                      const double* weight /* may be NULL */, const double* tol, void* partial,
                      double* out_max, int64_t* out_arg, double* out_wsum, int64_t* out_count,
                      double* out_wtot, void* stream);
+
+/* Vegetation fraction through the year (no counterpart in the reference, whose
+ * caller passes SHDFAC): row NMP_F_SHDFAC of static_f for a date from the
+ * static file's 12 monthly GREENFRAC rows, resident on the device, so a long
+ * run's canopy follows the calendar without a host copy of the row.  table12
+ * is 12 fp32 rows with leading dimension ld_tab (month m of column c at
+ * table12[m*ld_tab + c]; fp32 for both precisions, as the file stores f4),
+ * possibly offset by a range's first column; out_row is ncol elements of the
+ * engine precision T, e.g. static_f + NMP_F_SHDFAC*ld (+ the range's first
+ * column).  m0, m1 and w are the caller's: the two months whose mid-month values
+ * bracket the date and the weight of the later one (noahmp-1_amd/vegclim.py
+ * month_weights: t = 12*julian/yearlen - 0.5 in double, f = floor(t),
+ * m0 = f mod 12, m1 = (m0 + 1) mod 12, w = t - f).
+ * The operation order is part of this interface: per column c, in IEEE double,
+ * each operation rounded once (no fused multiply-add),
+ *   a = (double)table12[m0*ld_tab + c]      b = (double)table12[m1*ld_tab + c]
+ *   u = 1.0 - w        (formed once on the host side of the call)
+ *   r = (float)(u*a + w*b)                  (two rounded products, then one add)
+ *   out_row[c] = (T)r
+ * so the result is rounded once to fp32 and that fp32 value is widened to T:
+ * an fp64 engine sees the value a host that interpolates in fp32 storage and
+ * then converts gives it.  There are no special cases: w == 0, NaN, -0 and
+ * subnormals go through the formula (vegclim.py shdfac_host restates it in
+ * numpy, bit for bit).  One lane per column, one kernel enqueued on `stream`;
+ * the call neither synchronises nor allocates; elements ncol.. of out_row and
+ * every other row are untouched.  NMP_E_ARG, with nothing enqueued and the row
+ * untouched, for a NULL engine, ncol < 0, ld_tab < ncol, ld_tab >= 2^29 (so
+ * ncol above the limit too), m0 or m1 outside 0..11, w outside [0, 1) or NaN,
+ * or a NULL table12 or out_row with ncol > 0; ncol == 0 is NMP_OK with nothing
+ * enqueued. */
+int nmp_static_monthly(nmp_engine* eng, int64_t ncol, int64_t ld_tab, const float* table12,
+                       int m0, int m1, double w, void* out_row, void* stream);
 
 int nmp_run(nmp_engine* eng, int64_t ncol, int64_t ld, const float zsoil[4], float dt,
             float julian0, int32_t yearlen, int32_t nsteps, void* state, int32_t* isnow,

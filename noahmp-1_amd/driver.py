@@ -21,6 +21,10 @@ offline/noahmp_config.py has no time loop, forcing reader or writer, SURVEY
   with ``state_out`` each file also carries the selected groups of the land
   state -- soil, snow and canopy fields (layout.STATE_OUT), formed on the
   device from the state the output step left (nmp_state_output);
+  with ``veg_clim`` the vegetation fraction SHDFAC follows the static file's
+  monthly GREENFRAC climatology through the run, re-formed on the device from
+  the resident table (nmp_static_monthly; vegclim.py states the scheme) instead
+  of staying at the run's first instant;
   with ``regions`` each output step also writes the regions' weighted means of
   every output field as ``<YYYYMMDDHH>.REGIONS_DOMAIN1`` (nmp_region_reduce on
   the output block, on rank 0; ``write_grids=False`` then drops the grids);
@@ -56,7 +60,7 @@ import numpy as np
 import torch
 import torch.distributed as dist
 
-from . import cases, layout as L, ncio, shard, stateout, timeman
+from . import cases, layout as L, ncio, shard, stateout, timeman, vegclim
 from .config import Config
 from .engine import ColumnState, Engine, StreamShards
 from .feeds import (DeviceSyntheticForcing, ForcingUpload, HostFeed,  # noqa: F401  (re-exported)
@@ -130,7 +134,8 @@ class OfflineDriver:
                  regions=None, region_weights="area", write_grids: bool = True,
                  downscale: bool = False, lapse_rate: float = 0.0065, interp: bool = False,
                  hold=("RAINRATE",), sw_zenith: bool = True, cosz_floor: float = 0.05,
-                 prefetch: bool = True, state_out=None):
+                 prefetch: bool = True, state_out=None, veg_clim: str | None = None,
+                 greenfrac=None):
         """cols: this rank's columns (all of them on a single rank); under an
         initialised process group they must be the rank's shard_range block of
         the global column set.  ldasin_upload: with a provider that has
@@ -190,7 +195,28 @@ class OfflineDriver:
         and write them after the fluxes, a layered group as one variable over
         a layer dimension.  REGIONS files carry the fluxes and the groups that
         cannot hold the fill value.  Refused in a run that writes no output.
-        None (the default): every code path and output byte is as without it."""
+        None (the default): every code path and output byte is as without it.
+        veg_clim: "daily" or "step": SHDFAC (row NMP_F_SHDFAC of static_f, the
+        vegetated fraction of every column with opt_veg = 1; other opt_veg
+        values do not read it) follows `greenfrac`, the (12, ncol) monthly
+        climatology of this driver's own columns (ncio.read_greenfrac, in the
+        order of `cols`), through the run: the table goes up once, and before a
+        step whose instant -- the step's start with "step", 00:00 of its day
+        with "daily" (vegclim.quantise) -- differs from the one the row was
+        last formed for, each range forms its own columns of the row on its
+        stream ahead of its step (nmp_static_monthly; vegclim.shdfac_host is
+        the numpy form).  The row is a function of that instant alone: nothing
+        travels in restarts, and load_restart, a jump in time and spinup()'s
+        rewind re-form it.  Refused without a table or with one of another
+        shape.  None (the default): no table, no hook, every code path and
+        output byte is as without it."""
+        # (a bad veg_clim or table is refused before any device work)
+        self.veg_clim, gf_host = veg_clim, None
+        if veg_clim is not None:
+            vegclim.quantise(cfg.begdatetime, veg_clim)
+            if greenfrac is None:
+                raise ValueError("veg_clim needs greenfrac, the (12, ncol) monthly table")
+            gf_host = vegclim.check_table(greenfrac, int(np.asarray(cols.isnow).shape[0]))
         self.state_mask = 0
         if state_out is not None:
             self.state_mask = stateout.parse_groups(state_out)
@@ -217,6 +243,10 @@ class OfflineDriver:
         self.cs = ColumnState.from_host(cols, self.dev, self.dtype)
         # column ranges on their own streams: launch tails overlap (engine.StreamShards)
         self.ranges = StreamShards(self.engine, self.cs, streams)
+        # veg_clim: the resident climatology, and the instant SHDFAC was last formed for
+        self._veg_table, self._veg_key = None, None
+        if gf_host is not None:
+            self._veg_table = torch.as_tensor(gf_host, device=self.dev)
         total, first, rank0 = _shard_extent(self.cs.ncol, self.dev)
         if forcing == "device":
             # draws keyed by the global column index: the forcing of a column
@@ -287,7 +317,8 @@ class OfflineDriver:
     def from_files(cls, cfg: Config, device: int = 0, params: Params | None = None,
                    init: str | None = None, order: str | None = "lon-snow-type",
                    host_threads: int | None = None, forcing_grid: str | None = None,
-                   nearest=(), regions=None, region_weights="area", **kw) -> "OfflineDriver":
+                   nearest=(), regions=None, region_weights="area", veg_clim: str | None = None,
+                   **kw) -> "OfflineDriver":
         """The run the namelist describes: static file (cfg.constfile), initial
         state (cfg.initfile, or `init`) and LDASIN forcing (cfg.indir every
         cfg.input_frequency), netCDF-3 files in the layouts of ncio.py.
@@ -307,7 +338,10 @@ class OfflineDriver:
         (ncio.LdasinForcing; default NMP_HOST_THREADS, else 8).
         regions: the path of a region file on the run's grid (int REGION,
         optional double AREA; region_columns); region_weights "area" then
-        uses AREA if the file has it, else cos(latitude)."""
+        uses AREA if the file has it, else cos(latitude).
+        veg_clim: see __init__; the table is the static file's GREENFRAC
+        (ncio.read_greenfrac), laid out like every other per-column input:
+        the coherent order and this rank's block."""
         P = params or Params.builtin()
         grid, sf, si = ncio.read_static(cfg.constfile, P.as_dict(), cfg.begdatetime)
         st, isn, t0, step = ncio.read_state(init or cfg.initfile, grid)
@@ -319,6 +353,12 @@ class OfflineDriver:
             idx = perm[s0:s0 + cnt]
         cols = cases.ColumnSet(sf[:, idx], si[:, idx], st[:, idx], isn[idx], grid.lon_rad[idx],
                                *([None] * 6))
+        if veg_clim is not None:
+            vegclim.quantise(cfg.begdatetime, veg_clim)
+            gf = ncio.read_greenfrac(cfg.constfile, grid)
+            if gf is None:
+                raise ValueError(f"veg_clim needs GREENFRAC in the static file {cfg.constfile}")
+            kw = dict(kw, veg_clim=veg_clim, greenfrac=gf[:, idx])
         fkw = {}
         if forcing_grid is not None:
             fkw = dict(src=ncio.read_forcing_grid(os.fspath(forcing_grid)), nearest=nearest)
@@ -387,6 +427,7 @@ class OfflineDriver:
         so the next output's totals and means cover the steps from here."""
         self.ranges.join()  # no range may still be stepping the state being replaced
         self.feed.reset()   # resident blocks and read-ahead belong to the old time
+        self._veg_key = None  # veg_clim: SHDFAC is re-formed for the restart's time
         if path.endswith(".nc"):
             st, isn, self.t, self.step_index = ncio.read_state(path, self.grid,
                                                                self.cs.state.cpu().numpy().dtype)
@@ -463,6 +504,8 @@ class OfflineDriver:
                 dstep, post = self.accum.step(f, diag, out)
             if out and self.state_mask:
                 post = self._state_post(diag[self.nflux:], post)
+            if self._veg_table is not None:
+                pre = self._veg_pre(t0, pre)
             self.ranges.step(f, self.zsoil, self.dt, timeman.julian(t0), timeman.yearlen(t0.year),
                              dstep, level, after=after, pre=pre, post=post)
             self.feed.launched(t0, self.ranges.producers)
@@ -482,6 +525,24 @@ class OfflineDriver:
         torch.cuda.synchronize(self.dev)
         self.flush_output()
         return self
+
+    def _veg_pre(self, t0: datetime.datetime, first):
+        """StreamShards.step's `pre` of a step that starts at t0 with veg_clim:
+        `first` (the feed's, or None) as it is while SHDFAC stands for the
+        step's instant; else the range's columns of the row for that instant,
+        then `first`."""
+        when = vegclim.quantise(t0, self.veg_clim)
+        if when == self._veg_key:
+            return first
+        self._veg_key = when
+        m0, m1, w = vegclim.month_weights(when)
+        row = self.cs.static_f[L.STATIC_F.index("SHDFAC")]
+
+        def pre(st, rng):
+            self.engine.static_monthly(self._veg_table, m0, m1, w, row, stream=st, cols=rng)
+            if first is not None:
+                first(st, rng)
+        return pre
 
     def _state_post(self, rows: torch.Tensor, first):
         """StreamShards.step's `post` of an output step with state output:

@@ -540,6 +540,24 @@ class Engine:
                 res=torch.empty(4 * L.NDRIFT + 1, dtype=torch.int64, pin_memory=True))
         return b
 
+    # ---- vegetation fraction through the year (nmp_static_monthly) ---------------
+    def static_monthly(self, table: torch.Tensor, m0: int, m1: int, w: float,
+                       out_row: torch.Tensor, stream=None, cols: tuple[int, int] | None = None):
+        """nmp_static_monthly: out_row[c] (n,), engine precision = the monthly
+        climatology `table` (12, n) float32 between its rows m0 and m1 with the
+        later one's weight w, 0 <= w < 1 (vegclim.month_weights gives the three
+        for a date; vegclim.static_monthly_host is the numpy form).  out_row is
+        e.g. cs.static_f[L.STATIC_F.index("SHDFAC")], a row of a field-major
+        block.  cols=(lo, hi) writes only those columns, enqueued on `stream`."""
+        n = int(out_row.shape[0]) if out_row.dim() == 1 else -1
+        lo, hi = self._cols_range(n, cols)
+        self._check_block(table, (12, n), torch.float32, "table")
+        self._check_block(out_row, (n,), self.dtype, "out_row")
+        s = stream if stream is not None else torch.cuda.current_stream(self.device)
+        _lib.check(self._lib.nmp_static_monthly(self._h, hi - lo, n, _ptr(table, lo), int(m0),
+                                                int(m1), float(w), _ptr(out_row, lo),
+                                                C.c_void_p(s.cuda_stream)), "nmp_static_monthly")
+
     # ---- region-aggregated output (nmp_region_reduce) ---------------------------
     def region_reduce(self, fields: torch.Tensor, plan, sums: torch.Tensor,
                       means: torch.Tensor | None = None, stream=None):

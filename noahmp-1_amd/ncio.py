@@ -194,6 +194,21 @@ def read_static(path: str, params: dict, when: datetime.datetime):
         f.close()
 
 
+def read_greenfrac(path: str, grid: Grid):
+    """The static file's 12 monthly GREENFRAC grids as a (12, n) float32 table
+    of the grid's land points, in land-point order (the rows read_static
+    interpolates SHDFAC from; vegclim.shdfac_host forms the row for any date),
+    or None when the file has no GREENFRAC."""
+    f = _read(path)
+    try:
+        if "GREENFRAC" not in f.variables:
+            return None
+        gf = np.array(f.variables["GREENFRAC"][:])
+        return np.stack([grid.columns(gf[m]) for m in range(12)]).astype(np.float32)
+    finally:
+        f.close()
+
+
 def _month_weighted(g12: np.ndarray, when: datetime.datetime) -> np.ndarray:
     """Linear interpolation between mid-month values (a monthly climatology at `when`)."""
     ylen = timeman.yearlen(when.year)

@@ -10,6 +10,7 @@
                               [--nearest RAINRATE,SWDOWN]]
                              [--interp [--interp-hold VAR[,VAR]]
                               [--interp-sw zenith|linear|hold] [--cosz-floor X]]
+                             [--veg-clim [daily|step]]
 
 Reads the namelist like the reference (noahmp_amd.config.Config ==
 offline/noahmp_config.Config) and then does what the reference driver does
@@ -59,7 +60,7 @@ def _spinup(drv, cfg, a):
         print(f"spin-up: state written to {path}")
 
 
-def main(argv=None):
+def build_parser():
     ap = argparse.ArgumentParser(description="Noah-MP Land Surface Model (MI355X engine)")
     ap.add_argument("nmlfile", nargs="?", default=DEFAULT_NAMELIST_FILE, help="configuration file")
     ap.add_argument("--ncol", type=int, default=1)
@@ -121,6 +122,13 @@ def main(argv=None):
     ap.add_argument("--cosz-floor", type=float, default=0.05, metavar="X",
                     help="with --interp-sw zenith: lower bound of COSZ in the clearness ratio "
                          "SWDOWN / max(COSZ, X) (default 0.05)")
+    ap.add_argument("--veg-clim", nargs="?", const="daily", default=None,
+                    choices=("daily", "step"),
+                    help="netCDF cases: the vegetation fraction SHDFAC follows the static file's "
+                         "monthly GREENFRAC through the run, re-formed on the device once per "
+                         "model day (daily, the bare flag) or before every step (step), instead "
+                         "of staying at the run's first instant (nmp_static_monthly).  Only "
+                         "opt_veg = 1 reads SHDFAC: with other values the option has no effect")
     ap.add_argument("--spinup-loops", type=int, default=None, metavar="N",
                     help="before the run, spin the state up: run the period up to N times, "
                          "each pass from the state the pass before left, writing no output, "
@@ -137,6 +145,11 @@ def main(argv=None):
     ap.add_argument("--spinup-restart", action="store_true",
                     help="write the spun-up state at the start time as a restart file "
                          "(RESTART.<stamp>_DOMAIN1.spinup.nc, or .npz without a grid)")
+    return ap
+
+
+def main(argv=None):
+    ap = build_parser()
     a = ap.parse_args(argv)
     if a.spinup_loops is None and (a.spinup_tol is not None or a.spinup_min_loops is not None
                                    or a.spinup_map or a.spinup_restart):
@@ -180,15 +193,17 @@ def main(argv=None):
                 hold.append("SWDOWN")
             rkw.update(interp=True, hold=tuple(hold), sw_zenith=a.interp_sw == "zenith",
                        cosz_floor=a.cosz_floor)
+        if a.veg_clim:
+            rkw.update(veg_clim=a.veg_clim)
         drv =driver.OfflineDriver.from_files(cfg, device=a.device, params=P, init=a.restart,
                                               precision=a.precision, cosz=a.cosz,
                                               ingest=not a.no_ingest, accumulate=a.accumulate,
                                               **rkw)
         a.ncol = drv.cs.ncol
     else:
-        if a.regions or a.forcing_grid or a.interp:
-            ap.error("--regions, --forcing-grid and --interp need a run from files (the "
-                     "namelist's static_parameter_file)")
+        if a.regions or a.forcing_grid or a.interp or a.veg_clim:
+            ap.error("--regions, --forcing-grid, --interp and --veg-clim need a run from files "
+                     "(the namelist's static_parameter_file)")
         cols = cases.make_columns(a.ncol, a.kind, P.as_dict(), seed=0,
                                   julian=timeman.julian(cfg.begdatetime))
         drv = driver.OfflineDriver(cfg, cols, device=a.device, params=P,

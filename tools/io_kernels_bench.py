@@ -33,6 +33,8 @@ achieved HBM bandwidth against their algorithmic bytes, at 1,048,576 columns.
                            the state rows, writes 13
   drift_reduce             both passes: reads 7 drift rows and the weight
                            (36 B fp32, 64 B fp64) (spinup.algorithmic_bytes)
+  static_monthly           reads two of the table's 12 fp32 rows (8 B), writes
+                           the SHDFAC row (4 B fp32, 8 B fp64)
 
 The two gather/scatter kernels are timed with the grid points in the
 columns' own order (`point` = identity: coalesced) and fully shuffled (every
@@ -132,6 +134,7 @@ def main():
     so_cols = cases_mod.make_columns(n, "mixed", P.as_dict(), seed=0)
     so_cs = {4: ColumnState.from_host(so_cols, dev, torch.float32),
              8: ColumnState.from_host(so_cols, dev, torch.float64)}
+    vc_tab = torch.as_tensor(rng.random((12, n)).astype(np.float32), device=dev)
     out = []
     for prec in (4, 8):
         eng = Engine(Params.builtin(), L.CASE_NML_OPTIONS, device=0, precision=prec)
@@ -200,6 +203,10 @@ def main():
         dr_args = _drift_reduce_args(eng, sp_drift, sp_w, sp_tol)
         cases.append(("drift_reduce", "weights, both passes",
                       lambda: eng._lib.nmp_drift_reduce(*dr_args), n * sp_bytes["drift_reduce"]))
+        # vegetation fraction: SHDFAC between two months of the resident table
+        vc_row = torch.empty(n, dtype=dt, device=dev)
+        cases.append(("static_monthly", None,
+                      lambda: eng.static_monthly(vc_tab, 5, 6, 1 / 3, vc_row), n * (8 + prec)))
         for name, order, fn, nbytes in cases:
             if only and name not in only:
                 continue

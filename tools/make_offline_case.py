@@ -5,6 +5,7 @@ runs it from the files.
 
     python tools/make_offline_case.py case.nml [--ny 32 --nx 64 --kind conus]
                                       [--forcing-grid SY SX] [--closing-file]
+                                      [--seasonal-greenfrac]
 
 --forcing-grid SY SX: the LDASIN files are written on a coarser SY x SX
 rectilinear grid that covers the model grid, with a forcing-grid file
@@ -39,6 +40,10 @@ def main(argv=None):
     ap.add_argument("--closing-file", action="store_true",
                     help="also write the LDASIN file at enddatetime, which `noahmp_offline.py "
                          "--interp` reads as the last input interval's other end")
+    ap.add_argument("--seasonal-greenfrac", action="store_true",
+                    help="the static file's GREENFRAC gets a 12-month cycle that peaks in each "
+                         "hemisphere's summer (for `noahmp_offline.py --veg-clim`) instead of "
+                         "the columns' SHDFAC every month")
     a = ap.parse_args(argv)
     cfg = config.Config(a.nmlfile)
     lat = a.lat0 + a.dlat * np.arange(a.ny)[:, None] + 0.0 * np.arange(a.nx)[None, :]
@@ -54,7 +59,8 @@ def main(argv=None):
         if d:
             os.makedirs(d, exist_ok=True)
     os.makedirs(cfg.indir, exist_ok=True)
-    ncio.write_static(cfg.constfile, cols, grid)
+    ncio.write_static(cfg.constfile, cols, grid,
+                      greenfrac=_seasonal_greenfrac(cols) if a.seasonal_greenfrac else None)
     ncio.write_state(cfg.initfile, grid, cols.state, cols.isnow, cfg.begdatetime)
     fcols, fgrid, where = cols, grid, ""
     if a.forcing_grid:
@@ -67,6 +73,17 @@ def main(argv=None):
         t, k = t + every, k + 1
     print(f"{grid.n} columns, {k} LDASIN files in {cfg.indir}{where}; static {cfg.constfile}, "
           f"init {cfg.initfile}")
+
+
+def _seasonal_greenfrac(cols):
+    """(12, n) float32 mid-month GREENFRAC: the columns' SHDFAC at the peak of
+    their hemisphere's summer (July north of the equator, January south of
+    it), a fifth of it half a year later, a cosine between."""
+    shd = np.asarray(cols.static_f[2], np.float64)
+    peak = np.where(np.asarray(cols.static_f[0]) >= 0, 6.0, 0.0)
+    m = np.arange(12.0)[:, None]
+    g = shd[None, :] * (0.6 + 0.4 * np.cos(2.0 * np.pi * (m - peak[None, :]) / 12.0))
+    return np.clip(g, 0.0, 1.0).astype(np.float32)
 
 
 def _terrain(lat, lon, fine):

@@ -33,6 +33,10 @@ path), interleaved -- ms per step of every run, median and range per variant.
 
 --state-out-runs N times state output instead: N fresh runs each with
 state_out="all" and without, interleaved, reported the same way.
+
+--veg-clim-runs N times the vegetation fraction's updates instead: the case
+with a seasonal GREENFRAC, N fresh runs each without veg_clim and with
+veg_clim="step", interleaved, reported the same way.
 """
 import argparse
 import json
@@ -230,8 +234,49 @@ def state_out_runs(a, nml):
             "summary": summary, "driver": runs["plain"] + runs["state_out"]}
 
 
+def veg_clim_runs(a, nml):
+    """The case with a seasonal GREENFRAC: fresh runs without veg_clim and with
+    veg_clim="step" (the worst case: nmp_static_monthly before every step of
+    every range; "daily" enqueues it once per model day), interleaved; ms per
+    step of each run, and each variant's median and range.  --variants picks
+    other sets, e.g. "off" alone to time a tree without the option on a case
+    written before (--keep-case)."""
+    if not (a.keep_case and os.path.exists(config.Config(nml).constfile)):
+        import make_offline_case
+        make_offline_case.main([nml, "--ny", str(a.ny), "--nx", str(a.nx), "--kind", "mixed",
+                                "--seasonal-greenfrac"])
+    cfg = config.Config(nml)
+    names = [v for v in a.variants.split(",") if v]
+    runs = {v: [] for v in names}
+    for i in range(a.veg_clim_runs):
+        for name in names:
+            kw = {} if name == "off" else dict(veg_clim=name)
+            r, _, drv = time_driver(cfg, 4, True, a.warm, a.steps, a.threads, "device", True, **kw)
+            r["variant"], r["round"] = name, i
+            print(json.dumps(r), flush=True)
+            runs[name].append(r)
+            del drv
+    summary = {}
+    for name, rs in runs.items():
+        ms = sorted(r["ms_per_step"] for r in rs)
+        summary[name] = {"runs": len(ms), "median_ms_per_step": float(np.median(ms)),
+                         "min_ms_per_step": ms[0], "max_ms_per_step": ms[-1]}
+    print(json.dumps(summary), flush=True)
+    return {"case": f"{a.ny} x {a.nx} land points (mixed USGS/STAS columns, seasonal GREENFRAC), "
+                    "900-s steps, hourly LDASIN, 3-hourly LDASOUT; fp32, file bytes ingested on "
+                    "the device; fresh drivers, variants interleaved",
+            "summary": summary, "driver": [r for v in names for r in runs[v]]}
+
+
 def main():
     ap = argparse.ArgumentParser()
+    ap.add_argument("--veg-clim-runs", type=int, default=0, metavar="N",
+                    help="time N fresh runs each without veg_clim and with veg_clim='step', "
+                         "interleaved, instead")
+    ap.add_argument("--variants", default="off,step", metavar="NAME[,NAME]",
+                    help="with --veg-clim-runs: the variants to time (off, daily, step)")
+    ap.add_argument("--keep-case", action="store_true",
+                    help="with --veg-clim-runs: reuse the case files in --dir if they exist")
     ap.add_argument("--state-out-runs", type=int, default=0, metavar="N",
                     help="time N fresh runs each with and without state_out='all', interleaved, "
                          "instead")
@@ -251,8 +296,9 @@ def main():
     a = ap.parse_args()
     os.makedirs(a.dir, exist_ok=True)
     nml = write_namelist(a.dir)
-    if a.interp_runs or a.state_out_runs:
-        res = interp_runs(a, nml) if a.interp_runs else state_out_runs(a, nml)
+    if a.interp_runs or a.state_out_runs or a.veg_clim_runs:
+        res = (interp_runs(a, nml) if a.interp_runs else state_out_runs(a, nml)
+               if a.state_out_runs else veg_clim_runs(a, nml))
         if a.out:
             os.makedirs(os.path.dirname(os.path.abspath(a.out)), exist_ok=True)
             with open(a.out, "w") as f:
