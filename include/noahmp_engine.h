@@ -41,6 +41,9 @@
  * nmp_static_monthly          no counterpart: the vegetation fraction SHDFAC of a date from the
  *                             12-month GREENFRAC climatology (fveg = SHDFAC with opt_veg = 1,
  *                             core/module_noahmp_func.f90:366-368), on the device
+ * nmp_extremes_update,        no counterpart: an output interval's running maximum and minimum
+ *   nmp_extremes_output       of per-column series (fluxes, forcing, state rows) and the time
+ *                             each occurred, on the device
  * nmp_frh2o, nmp_frh2o_host   frh2o (public routine)       core/module_noahmp_func.f90:4494-4598
  * nmp_calhum, nmp_calhum_host calhum (public by default)     core/module_noahmp_func.f90:3958-3984
  * nmp_state_from_aos          layout bridge from noahmp_state_t records
@@ -804,6 +807,68 @@ int nmp_drift_reduce(nmp_engine* eng, int64_t ncol, int64_t ld_drift, const void
  * enqueued. */
 int nmp_static_monthly(nmp_engine* eng, int64_t ncol, int64_t ld_tab, const float* table12,
                        int m0, int m1, double w, void* out_row, void* stream);
+
+/* Interval extremes (no counterpart in the reference, which writes no output):
+ * the running maximum and minimum of per-column series over an output
+ * interval, and the step of the interval that set each of them -- the day's
+ * highest and lowest 2-m temperature, the peak runoff rate and when it fell.
+ *
+ * Series.  A series is one value per column per step, named by a pair
+ * (kind, row): NMP_EXT_SRC_DIAG = row NMP_O_* of the step's NMP_NDIAG_OUT-row
+ * flux block `diag` (a step at NMP_DIAG_OUT), NMP_EXT_SRC_FORCING = row NMP_A_*
+ * of the step's NMP_NFORCING-row `forcing` block, NMP_EXT_SRC_STATE = row
+ * NMP_S_* (0..55) of the `state` the step left.  `series` is a HOST array of
+ * nseries pairs, series[2*s] = kind and series[2*s + 1] = row, 1 <= nseries <=
+ * NMP_EXT_MAXSERIES; the three blocks share the leading dimension ld.
+ *
+ * Resident state, leading dimension ld_ext: `val`, 2*nseries x ld_ext of the
+ * engine precision T, row 2*s the running maximum of series s and row 2*s + 1
+ * its running minimum; `when`, int32 of the same shape, the 1-based number
+ * within the interval of the step that set each of them.
+ *
+ * nmp_extremes_update: one kernel.  k >= 1 is the number of this step within
+ * its interval.  Per column and series, with v the series' value, the rule is
+ * part of this interface:
+ *   k == 1:  max = min = v, both when = 1.  A value of any kind is taken, NaN
+ *            included: no reset launch exists or is needed.
+ *   k > 1:   the max takes v, and its when = k, iff (v > max) || (max != max && v == v);
+ *            the min takes v, and its when = k, iff (v < min) || (min != min && v == v).
+ * So the first occurrence wins a tie; -0 and +0 tie, and whichever came first
+ * stays with its sign bit; NaN survives only while every value so far was NaN,
+ * and its when is then 1.  Values are stored as loaded: no arithmetic, no
+ * rounding.  diag may be NULL when no series has kind DIAG; the same holds for
+ * forcing and for state.
+ *
+ * nmp_extremes_output: one kernel.  `stats` is a HOST array of nseries bit
+ * masks of NMP_EXT_MAX, NMP_EXT_MIN, NMP_EXT_TMAX, NMP_EXT_TMIN.  It writes the
+ * rows of `out` (leading dimension ld_out, engine precision) in series order
+ * and within a series in bit order MAX, MIN, TMAX, TMIN, for the bits that are
+ * set: a value row is val as stored; a time row is (T)((double)when * dt), one
+ * rounded product and one conversion -- the seconds from the interval's start
+ * to the end of the step that produced the extreme (dt: the step in seconds).
+ * It changes neither val nor when.
+ *
+ * Both: device pointers, possibly offset by a range's first column; one lane
+ * per column, enqueued on `stream`; the calls neither synchronise nor
+ * allocate; elements ncol.. of every row, and rows not named, are untouched
+ * (noahmp-1_amd/extremes.py update_host / output_host restate both in numpy,
+ * bit for bit).  NMP_E_ARG, with nothing enqueued, for a NULL engine,
+ * ncol < 0, ld, ld_ext or ld_out below ncol or at or above 2^29, nseries
+ * outside 1..NMP_EXT_MAXSERIES, a kind outside the three, a row outside its
+ * block, a stats mask of 0 or with a bit above NMP_EXT_TMIN, k < 1, dt not
+ * finite or <= 0, a NULL series or stats, or -- with ncol > 0 -- a NULL val,
+ * when or out or a NULL block that a named series needs; ncol == 0 with
+ * otherwise valid arguments is NMP_OK with nothing enqueued. */
+#define NMP_EXT_MAXSERIES 32
+enum { NMP_EXT_SRC_DIAG = 0, NMP_EXT_SRC_FORCING = 1, NMP_EXT_SRC_STATE = 2 };
+enum { NMP_EXT_MAX = 1, NMP_EXT_MIN = 2, NMP_EXT_TMAX = 4, NMP_EXT_TMIN = 8 };
+int nmp_extremes_update(nmp_engine* eng, int64_t ncol, int64_t ld, int nseries,
+                        const int32_t* series, const void* diag /* may be NULL */,
+                        const void* forcing /* may be NULL */, const void* state /* may be NULL */,
+                        int32_t k, void* val, int32_t* when, int64_t ld_ext, void* stream);
+int nmp_extremes_output(nmp_engine* eng, int64_t ncol, int nseries, const int32_t* stats,
+                        double dt, const void* val, const int32_t* when, int64_t ld_ext,
+                        void* out, int64_t ld_out, void* stream);
 
 int nmp_run(nmp_engine* eng, int64_t ncol, int64_t ld, const float zsoil[4], float dt,
             float julian0, int32_t yearlen, int32_t nsteps, void* state, int32_t* isnow,

@@ -21,6 +21,10 @@ offline/noahmp_config.py has no time loop, forcing reader or writer, SURVEY
   with ``state_out`` each file also carries the selected groups of the land
   state -- soil, snow and canopy fields (layout.STATE_OUT), formed on the
   device from the state the output step left (nmp_state_output);
+  with ``extremes`` each file also carries the interval's extremes of the
+  selected series -- their maximum, their minimum and the time each occurred
+  (extremes.py), tracked on the device after every step (nmp_extremes_update /
+  nmp_extremes_output);
   with ``veg_clim`` the vegetation fraction SHDFAC follows the static file's
   monthly GREENFRAC climatology through the run, re-formed on the device from
   the resident table (nmp_static_monthly; vegclim.py states the scheme) instead
@@ -60,13 +64,13 @@ import numpy as np
 import torch
 import torch.distributed as dist
 
-from . import cases, layout as L, ncio, shard, stateout, timeman, vegclim
+from . import cases, extremes as xtr, layout as L, ncio, shard, stateout, timeman, vegclim
 from .config import Config
 from .engine import ColumnState, Engine, StreamShards
 from .feeds import (DeviceSyntheticForcing, ForcingUpload, HostFeed,  # noqa: F401  (re-exported)
                     SyntheticForcing, feed_kind, make_feed)
 from .order import coherent_order
-from .output import Accumulation, OutputWriter
+from .output import Accumulation, Extremes, OutputWriter
 from .params import Params
 from .regions import area_weights, plan_from_args
 
@@ -135,7 +139,7 @@ class OfflineDriver:
                  downscale: bool = False, lapse_rate: float = 0.0065, interp: bool = False,
                  hold=("RAINRATE",), sw_zenith: bool = True, cosz_floor: float = 0.05,
                  prefetch: bool = True, state_out=None, veg_clim: str | None = None,
-                 greenfrac=None):
+                 greenfrac=None, extremes=None):
         """cols: this rank's columns (all of them on a single rank); under an
         initialised process group they must be the rank's shard_range block of
         the global column set.  ldasin_upload: with a provider that has
@@ -209,7 +213,23 @@ class OfflineDriver:
         travels in restarts, and load_restart, a jump in time and spinup()'s
         rewind re-form it.  Refused without a table or with one of another
         shape.  None (the default): no table, no hook, every code path and
-        output byte is as without it."""
+        output byte is as without it.
+        extremes: "T2M,TRAD:max,PRCP:max+tmax", or an iterable of names or
+        (name, stats) pairs (extremes.parse: the output fluxes, the forcing
+        rows, the single-row state fields and the soil layers SMC1..4,
+        SH2O1..4, STC1..4; stats of max, min, tmax, tmin, default max+min).
+        Every step then folds its values into the interval's running maxima and
+        minima on each range's stream right after the step (nmp_extremes_update,
+        after nmp_accumulate when accumulating), and output steps write the
+        rows <NAME>_MAX, _MIN, _TMAX, _TMIN (nmp_extremes_output; times in
+        seconds from the interval's start to the end of the step that set the
+        extreme) after the fluxes and the budget rows and before the state
+        rows.  With a series of the output fluxes every step writes its fluxes
+        (DIAG_OUT_LEVEL; into the scratch block accumulation uses when both are
+        on); without one the steps between output steps stay at DIAG_NONE.
+        REGIONS files carry the rows; restarts carry the interval so far
+        (save_restart).  Refused in a run that writes no output.  None (the
+        default): every code path and output byte is as without it."""
         # (a bad veg_clim or table is refused before any device work)
         self.veg_clim, gf_host = veg_clim, None
         if veg_clim is not None:
@@ -222,6 +242,11 @@ class OfflineDriver:
             self.state_mask = stateout.parse_groups(state_out)
             if not write or cfg.output_interval is None:
                 raise ValueError("state_out needs a run that writes output")
+        ext_series = None
+        if extremes is not None:
+            ext_series = xtr.parse(extremes)
+            if not write or cfg.output_interval is None:
+                raise ValueError("extremes needs a run that writes output")
         if not write_grids and regions is None:
             raise ValueError("write_grids=False needs regions: the run would write nothing")
         # (a bad cosz, downscale or interp is refused before any device work)
@@ -265,17 +290,25 @@ class OfflineDriver:
         self.accumulate = bool(accumulate)
         self.out_names = L.DIAG_OUT_ACC if self.accumulate else L.DIAG_OUT
         self.nflux, region_rows = len(self.out_names), None
+        # the interval's extremes: their rows follow the fluxes (and the budget rows)
+        self.extremes, self.next = None, 0
+        if ext_series is not None:
+            self.extremes = Extremes(self.engine, self.cs, ext_series, self.dt,
+                                     scratch=not self.accumulate)
+            self.out_names = list(self.out_names) + self.extremes.names
+            self.next = len(self.extremes.names)
         if self.state_mask:
-            # the block's rows: the fluxes, then the selected state rows, the
-            # groups that can hold the fill value last; the regions stop before them
+            # the block's rows: the fluxes, the extremes rows, then the selected
+            # state rows, the groups that can hold the fill value last; the
+            # regions stop before them
             self.out_names = list(self.out_names) + stateout.row_names(self.state_mask)
-            region_rows = self.nflux + stateout.nofill_rows(self.state_mask)
+            region_rows = self.nflux + self.next + stateout.nofill_rows(self.state_mask)
         nout = len(self.out_names)
         self.diag = torch.zeros((nout, self.cs.ncol), dtype=self.dtype, device=self.dev)
         self.accum = None
         if self.accumulate:
             self.accum = Accumulation(self.engine, self.cs, self.dt)
-        if (self.accumulate or self.state_mask) and grid is not None:
+        if (self.accumulate or self.state_mask or self.extremes is not None) and grid is not None:
             # a grid whose 35 fields or state rows do not pass the classic
             # format's offsets fails here, not on a writer thread after the
             # first interval
@@ -380,6 +413,8 @@ class OfflineDriver:
             a = ncio.read_accum(init or cfg.initfile, grid)
             if a is not None:  # a restart written part way through an interval
                 drv.accum.restore(a, idx)
+        if drv.extremes is not None:
+            drv.extremes.restore(ncio.read_extremes(init or cfg.initfile, grid), idx)
         return drv
 
     @property
@@ -401,18 +436,27 @@ class OfflineDriver:
         """With accumulation on, the interval so far travels with the state:
         the accumulators, the interval's beginning storage and the number of
         steps accumulated (npz: arrays acc, stor_beg, acc_steps; netCDF:
-        ncio.write_state's accum)."""
+        ncio.write_state's accum).  With extremes on, so do the running
+        extremes, the steps that set them, the interval's step count and the
+        spec (npz: arrays ext_val, ext_when, ext_steps, ext_spec; netCDF:
+        ncio.write_state's extremes)."""
         self.ranges.join()
         accum = self.accum.state() if self.accum is not None else None
+        ext = self.extremes.state() if self.extremes is not None else None
         if path.endswith(".nc"):
             if accum is not None:
                 accum = (self.to_grid_order(accum[0]), self.to_grid_order(accum[1]), accum[2])
+            if ext is not None:
+                ext = (self.to_grid_order(ext[0]), self.to_grid_order(ext[1]), ext[2], ext[3])
             ncio.write_state(path, self.grid, self.to_grid_order(self.cs.state.cpu().numpy()),
                              self.to_grid_order(self.cs.isnow.cpu().numpy()), self.t,
-                             self.step_index, accum=accum)
+                             self.step_index, accum=accum, extremes=ext)
             return
         extra = {} if accum is None else dict(acc=accum[0], stor_beg=accum[1],
                                               acc_steps=np.int64(accum[2]))
+        if ext is not None:
+            extra.update(ext_val=ext[0], ext_when=ext[1], ext_steps=np.int64(ext[2]),
+                         ext_spec=np.array(ext[3]))
         np.savez(path, **extra, time=np.array(self.t.isoformat()), step=np.int64(self.step_index),
                  state=self.cs.state.cpu().numpy(), isnow=self.cs.isnow.cpu().numpy(),
                  static_f=self.cs.static_f.cpu().numpy(), static_i=self.cs.static_i.cpu().numpy(),
@@ -424,7 +468,11 @@ class OfflineDriver:
         accumulation state (save_restart of an accumulating run) resumes that
         interval; one without it starts a fresh interval at this point: zero
         accumulators and the beginning storage formed from the loaded state,
-        so the next output's totals and means cover the steps from here."""
+        so the next output's totals and means cover the steps from here.
+        With extremes on, likewise: a restart that carries an interval's
+        extremes under this run's spec resumes it; one without them, or with
+        another spec, starts a fresh interval here, so the next output's
+        extremes cover the steps from here."""
         self.ranges.join()  # no range may still be stepping the state being replaced
         self.feed.reset()   # resident blocks and read-ahead belong to the old time
         self._veg_key = None  # veg_clim: SHDFAC is re-formed for the restart's time
@@ -437,6 +485,8 @@ class OfflineDriver:
             self.cs.isnow.copy_(torch.as_tensor(np.ascontiguousarray(isn[idx]), device=self.dev))
             if self.accum is not None:
                 self.accum.restore(ncio.read_accum(path, self.grid), idx)
+            if self.extremes is not None:
+                self.extremes.restore(ncio.read_extremes(path, self.grid), idx)
             self._start = (self.t, self.step_index)
             return
         with np.load(path, allow_pickle=False) as z:
@@ -449,6 +499,9 @@ class OfflineDriver:
             if self.accum is not None:
                 self.accum.restore((z["acc"], z["stor_beg"], int(z["acc_steps"]))
                                    if "acc" in z.files else None)
+            if self.extremes is not None:
+                self.extremes.restore((z["ext_val"], z["ext_when"], int(z["ext_steps"]),
+                                       str(z["ext_spec"])) if "ext_val" in z.files else None)
         self._start = (self.t, self.step_index)
 
     # ---- time loop -----------------------------------------------------------------
@@ -497,13 +550,21 @@ class OfflineDriver:
             dstep, level, post = None, L.DIAG_NONE, None
             if out:
                 dstep, level = diag, L.DIAG_OUT_LEVEL
-                if self.state_mask:
+                if self.state_mask or self.next:
                     dstep = diag[:L.NDIAG_OUT]
             if self.accum is not None:  # every step writes its fluxes
                 level = L.DIAG_OUT_LEVEL
                 dstep, post = self.accum.step(f, diag, out)
+            ext = self.extremes
+            if ext is not None:
+                if ext.need_diag and dstep is None:
+                    # a step between output steps, no accumulation: its fluxes
+                    # go to the extremes' own scratch block
+                    dstep, level = ext.scratch, L.DIAG_OUT_LEVEL
+                post = ext.step(f, dstep if ext.need_diag else None,
+                                diag[self.nflux:self.nflux + self.next] if out else None, post)
             if out and self.state_mask:
-                post = self._state_post(diag[self.nflux:], post)
+                post = self._state_post(diag[self.nflux + self.next:], post)
             if self._veg_table is not None:
                 pre = self._veg_pre(t0, pre)
             self.ranges.step(f, self.zsoil, self.dt, timeman.julian(t0), timeman.yearlen(t0.year),
@@ -688,6 +749,8 @@ class OfflineDriver:
         self.feed.reset()   # resident blocks and read-ahead belong to the old time
         if self.accum is not None:
             self.accum.restore(None)
+        if self.extremes is not None:
+            self.extremes.restore(None)
 
     def _spinup_record(self, k: int, res, tol_arr):
         """The loop's record from this rank's reduction; under a process group

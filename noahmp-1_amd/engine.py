@@ -558,6 +558,58 @@ class Engine:
                                                 int(m1), float(w), _ptr(out_row, lo),
                                                 C.c_void_p(s.cuda_stream)), "nmp_static_monthly")
 
+    # ---- interval extremes (nmp_extremes_update / nmp_extremes_output) -----------
+    def extremes_update(self, kind_rows, k: int, val: torch.Tensor, when: torch.Tensor,
+                        diag: torch.Tensor | None = None, forcing: torch.Tensor | None = None,
+                        state: torch.Tensor | None = None, stream=None,
+                        cols: tuple[int, int] | None = None):
+        """nmp_extremes_update: step k >= 1 of an output interval into the
+        running extremes val (2*nseries, n), engine precision, and when
+        (2*nseries, n) int32 -- row 2s the maximum of series s, row 2s + 1 its
+        minimum.  kind_rows: the series' (kind, row) pairs (extremes.pairs);
+        diag (NDIAG_OUT, n), forcing (NFORCING, n) and state (NSTATE, n) are the
+        step's blocks, None where no series names one.  extremes.update_host
+        is the numpy form.  cols=(lo, hi) updates only those columns, enqueued
+        on `stream`."""
+        kr = np.ascontiguousarray(np.asarray(kind_rows, np.int32).reshape(-1, 2))
+        ns, n = int(kr.shape[0]), int(val.shape[1]) if val.dim() == 2 else -1
+        lo, hi = self._cols_range(n, cols)
+        self._check_block(val, (2 * ns, n), self.dtype, "val")
+        self._check_block(when, (2 * ns, n), torch.int32, "when")
+        for t, rows, what in ((diag, L.NDIAG_OUT, "diag"), (forcing, L.NFORCING, "forcing"),
+                              (state, L.NSTATE, "state")):
+            if t is not None:
+                self._check_block(t, (rows, n), self.dtype, what)
+        s = stream if stream is not None else torch.cuda.current_stream(self.device)
+        _lib.check(self._lib.nmp_extremes_update(
+            self._h, hi - lo, n, ns, kr.ctypes.data_as(C.POINTER(C.c_int32)), _ptr(diag, lo),
+            _ptr(forcing, lo), _ptr(state, lo), int(k), _ptr(val, lo), _ptr(when, lo), n,
+            C.c_void_p(s.cuda_stream)), "nmp_extremes_update")
+
+    def extremes_output(self, stats, dt: float, val: torch.Tensor, when: torch.Tensor,
+                        out_rows: torch.Tensor, stream=None,
+                        cols: tuple[int, int] | None = None):
+        """nmp_extremes_output: the output rows of the series' stat masks
+        `stats` (extremes.masks; in series order, within a series MAX, MIN,
+        TMAX, TMIN) from val and when into out_rows (the masks' bits in all,
+        n), engine precision: values as stored, times (T)((double)when * dt)
+        seconds.  out_rows may be rows of a block (a contiguous row slice).
+        extremes.output_host is the numpy form.  cols=(lo, hi) writes only
+        those columns, enqueued on `stream`."""
+        m = np.ascontiguousarray(np.asarray(stats, np.int32).reshape(-1))
+        ns, n = int(m.shape[0]), int(val.shape[1]) if val.dim() == 2 else -1
+        lo, hi = self._cols_range(n, cols)
+        self._check_block(val, (2 * ns, n), self.dtype, "val")
+        self._check_block(when, (2 * ns, n), torch.int32, "when")
+        if all(0 < int(x) < 16 for x in m):   # (the library refuses any other mask)
+            nrow = sum(bin(int(x)).count("1") for x in m)
+            self._check_block(out_rows, (nrow, n), self.dtype, "out_rows")
+        s = stream if stream is not None else torch.cuda.current_stream(self.device)
+        _lib.check(self._lib.nmp_extremes_output(
+            self._h, hi - lo, ns, m.ctypes.data_as(C.POINTER(C.c_int32)), float(dt),
+            _ptr(val, lo), _ptr(when, lo), n, _ptr(out_rows, lo), n,
+            C.c_void_p(s.cuda_stream)), "nmp_extremes_output")
+
     # ---- region-aggregated output (nmp_region_reduce) ---------------------------
     def region_reduce(self, fields: torch.Tensor, plan, sums: torch.Tensor,
                       means: torch.Tensor | None = None, stream=None):

@@ -66,6 +66,14 @@ assert NXGROUP == 21 and NXROWS_NOFILL == 32 and NXROWS == 39
 # the six 2-D variables of the CARBON group, in row order
 CARBON_POOLS = ["LFMASS", "RTMASS", "STMASS", "WOOD", "STBLCP", "FASTCP"]
 
+# interval extremes (nmp_extremes_update / nmp_extremes_output): a series'
+# source block (NMP_EXT_SRC_*), the stat bits of its output rows (NMP_EXT_*, in
+# row order) and the most series a call takes (NMP_EXT_MAXSERIES)
+EXT_SRC_DIAG, EXT_SRC_FORCING, EXT_SRC_STATE = 0, 1, 2
+EXT_MAX, EXT_MIN, EXT_TMAX, EXT_TMIN = 1, 2, 4, 8
+EXT_STATS = {"MAX": EXT_MAX, "MIN": EXT_MIN, "TMAX": EXT_TMAX, "TMIN": EXT_TMIN}
+EXT_MAXSERIES = 32
+
 # spin-up drift (nmp_state_drift / nmp_drift_reduce): the tracked values'
 # rows (NMP_K_*: name -> first row) and the drift groups (NMP_G_*) with the
 # units of their drift

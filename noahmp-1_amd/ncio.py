@@ -220,13 +220,18 @@ def _month_weighted(g12: np.ndarray, when: datetime.datetime) -> np.ndarray:
 
 # ---- state (initialization / restart) ----------------------------------------------
 def write_state(path: str, grid: Grid, state: np.ndarray, isnow: np.ndarray,
-                t: datetime.datetime, step: int = 0, accum=None):
+                t: datetime.datetime, step: int = 0, accum=None, extremes=None):
     """SoA state (56, n) + ISNOW on the grid; layer fields get a layer dimension.
     accum: (acc (NACC, n) float64, stor_beg (n,), steps) of an accumulating run
     part way through an output interval (driver.OfflineDriver(accumulate=True)),
     stored as double variables ACC_<name> (layout.ACC) and STOR_BEG and the
     global attribute accum_steps; read_accum reads them, read_state ignores
-    them."""
+    them.
+    extremes: (val (2*nseries, n), when (2*nseries, n) int32, steps, spec) of a
+    run that tracks interval extremes (driver.OfflineDriver(extremes=...)),
+    stored as variables EXT_<NAME>_MAX / _MIN in val's precision, EXTW_<NAME>_MAX
+    / _MIN (int) and the global attributes extremes_steps and extremes_spec;
+    read_extremes reads them, read_state ignores them."""
     ny, nx = grid.shape
     f = netcdf_file(path, "w")
     try:
@@ -260,6 +265,42 @@ def write_state(path: str, grid: Grid, state: np.ndarray, isnow: np.ndarray,
                 v[:] = grid.scatter(row.astype(np.float64), fill)
             v = f.createVariable("STOR_BEG", "f8", dims)
             v[:] = grid.scatter(stor_beg.astype(np.float64), fill)
+        if extremes is not None:
+            val, when, nsteps, spec = extremes
+            names = _extremes_names(spec)
+            assert val.shape == when.shape == (len(names), grid.n), (val.shape, when.shape)
+            f.extremes_steps = np.int32(nsteps)
+            f.extremes_spec = str(spec)
+            xkind = "f8" if val.dtype == np.float64 else "f4"
+            for name, vrow, wrow in zip(names, val, when):
+                v = f.createVariable(f"EXT_{name}", xkind, dims)
+                v[:] = grid.scatter(vrow, np.asarray(FILL, xkind))
+                v = f.createVariable(f"EXTW_{name}", "i4", dims)
+                v[:] = grid.scatter(wrow.astype(np.int32), 0)
+    finally:
+        f.close()
+
+
+def _extremes_names(spec: str) -> list:
+    """<NAME>_MAX, <NAME>_MIN of every series of the spec: the rows of a run's
+    running extremes (val and when, row 2s the maximum of series s)."""
+    from . import extremes as X
+    return [f"{s.name}_{m}" for s in X.parse(spec) for m in ("MAX", "MIN")]
+
+
+def read_extremes(path: str, grid: Grid):
+    """(val (2*nseries, n), when (2*nseries, n) int32, steps, spec) of a state
+    file write_state stored a run's interval extremes in, or None when the file
+    carries none (an initialization file, a run without the option)."""
+    f = _read(path)
+    try:
+        if not hasattr(f, "extremes_steps") or not hasattr(f, "extremes_spec"):
+            return None
+        spec = f.extremes_spec.decode() if isinstance(f.extremes_spec, bytes) else f.extremes_spec
+        names = _extremes_names(spec)
+        val = np.stack([grid.columns(np.array(f.variables[f"EXT_{n}"][:])) for n in names])
+        when = np.stack([grid.columns(np.array(f.variables[f"EXTW_{n}"][:])) for n in names])
+        return val, when.astype(np.int32), int(f.extremes_steps), str(spec)
     finally:
         f.close()
 

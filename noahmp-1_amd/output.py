@@ -141,6 +141,73 @@ class OutputWriter:
                 f.result()
 
 
+class Extremes:
+    """An output interval's extremes (extremes.py), on the device: the running
+    maxima and minima `val` of the selected series, `when` (the step of the
+    interval that set each) and `k`, the steps taken so far.  Only with a
+    series of the output fluxes, and only when no accumulation lends its own,
+    a scratch block `scratch` for the fluxes of the steps between output
+    steps."""
+
+    def __init__(self, engine, cs, series, dt: float, scratch: bool):
+        from . import extremes as X
+        self.engine, self.cs, self.dt, self.series = engine, cs, dt, list(series)
+        self.spec = X.spec_string(self.series)
+        self.kind_rows, self.stats = X.pairs(self.series), X.masks(self.series)
+        self.names, self.need_diag = X.row_names(self.series), X.has_diag(self.series)
+        self.need_state = any(s.kind == L.EXT_SRC_STATE for s in self.series)
+        self.need_forcing = any(s.kind == L.EXT_SRC_FORCING for s in self.series)
+        n, dev, dtype = cs.ncol, cs.state.device, cs.state.dtype
+        self.val = torch.zeros((2 * len(self.series), n), dtype=dtype, device=dev)
+        self.when = torch.zeros((2 * len(self.series), n), dtype=torch.int32, device=dev)
+        self.scratch = None
+        if scratch and self.need_diag:
+            self.scratch = torch.zeros((L.NDIAG_OUT, n), dtype=dtype, device=dev)
+        self.k = 0
+
+    def state(self):
+        """(val, when, k, spec) of the interval so far, on the host: what a restart carries."""
+        return self.val.cpu().numpy(), self.when.cpu().numpy(), self.k, self.spec
+
+    def restore(self, state, idx=slice(None)):
+        """`state` (state(), of the columns `idx` picks) resumes its interval
+        if it was taken with this run's spec; None, or another spec, starts a
+        fresh one: the next step is the interval's first and takes any value."""
+        self.k = 0
+        if state is None or str(state[3]) != self.spec:
+            return
+        dev = self.val.device
+        dt = np.float32 if self.val.dtype == torch.float32 else np.float64
+        self.val.copy_(torch.as_tensor(np.ascontiguousarray(state[0][:, idx], dt), device=dev))
+        self.when.copy_(torch.as_tensor(np.ascontiguousarray(state[1][:, idx], np.int32),
+                                        device=dev))
+        self.k = int(state[2])
+
+    def step(self, f, fluxes, rows, first):
+        """One more step: StreamShards.step's `post` -- `first` (the
+        accumulation's, or None), then this step into the running extremes
+        from its fluxes block `fluxes` (None without a flux series), its
+        forcing `f` and the state it left; at an output step (rows: the output
+        block's extremes rows) also the interval's rows, and the next step
+        begins a new interval."""
+        self.k += 1
+        k = self.k
+        if rows is not None:
+            self.k = 0
+        state = self.cs.state if self.need_state else None
+        forcing = f if self.need_forcing else None
+
+        def post(st, rng):
+            if first is not None:
+                first(st, rng)
+            self.engine.extremes_update(self.kind_rows, k, self.val, self.when, fluxes, forcing,
+                                        state, stream=st, cols=rng)
+            if rows is not None:
+                self.engine.extremes_output(self.stats, self.dt, self.val, self.when, rows,
+                                            stream=st, cols=rng)
+        return post
+
+
 class Accumulation:
     """An output interval's accumulated output (layout.BUDGET), on the device:
     the accumulators `acc`, the scratch block `acc_diag` for the fluxes of the

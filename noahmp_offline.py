@@ -88,6 +88,13 @@ def build_parser():
                          "soil, snow and canopy fields (SOIL_M, SOIL_W, SOIL_T, SNEQV, SNOWH, TG, "
                          "TV, LAI, SAI, ZWT, WA, CANWAT, ISNOW, SNOWLIQ, TWS, SOILSAT, ROOT_M, "
                          "CARBON, SNOW_T, SNOW_Z, SNOWT_AVG), or all of them")
+    ap.add_argument("--extremes", default=None, metavar="NAME[:STAT[+STAT]][,NAME...]",
+                    help="also write each output interval's extremes of the named series: an "
+                         "output flux (FSH, T2M, RUNSRF, ...), a forcing row (PRCP, SFCTMP, ...), "
+                         "a state field (TG, SNEQV, ...) or a soil layer (SMC1..4, SH2O1..4, "
+                         "STC1..4), each with stats of max, min, tmax, tmin (default max+min), "
+                         "e.g. T2M,TRAD:max,PRCP:max+tmax -- variables <NAME>_MAX, _MIN and the "
+                         "seconds into the interval at which each occurred, _TMAX, _TMIN")
     ap.add_argument("--regions", default=None, metavar="FILE",
                     help="netCDF cases: a region file on the run's grid (int REGION, optional "
                          "double AREA); every output time then also writes the regions' "
@@ -178,6 +185,13 @@ def main(argv=None):
         except ValueError as e:
             ap.error(str(e))
         skw = dict(state_out=a.state_out)
+    if a.extremes is not None:
+        from noahmp_amd import extremes
+        try:
+            extremes.parse(a.extremes)
+        except ValueError as e:
+            ap.error(str(e))
+        skw.update(extremes=a.extremes)
     if os.path.isfile(cfg.constfile):
         rkw = dict(skw)
         if a.regions:

@@ -35,6 +35,14 @@ achieved HBM bandwidth against their algorithmic bytes, at 1,048,576 columns.
                            (36 B fp32, 64 B fp64) (spinup.algorithmic_bytes)
   static_monthly           reads two of the table's 12 fp32 rows (8 B), writes
                            the SHDFAC row (4 B fp32, 8 B fp64)
+  accumulate               reads 16 flux rows and PRCP, reads and writes the 17
+                           double accumulators (340 B fp32, 408 B fp64)
+  extremes_update          a step past the interval's first that sets no new
+                           extreme: per series reads the value and the running
+                           maximum and minimum (12 B fp32, 24 B fp64), writes
+                           nothing; with 4 and with 16 series
+  extremes_output          every stat of every series: reads val and when
+                           (16 B fp32, 24 B fp64 per series), writes 4 rows
 
 The two gather/scatter kernels are timed with the grid points in the
 columns' own order (`point` = identity: coalesced) and fully shuffled (every
@@ -58,7 +66,8 @@ import numpy as np  # noqa: E402
 import torch  # noqa: E402
 
 import noahmp_pkg  # noqa: E402,F401
-from noahmp_amd import cases as cases_mod, layout as L, spinup, stateout, timeman  # noqa: E402
+from noahmp_amd import (cases as cases_mod, extremes as xtr, layout as L, spinup,  # noqa: E402
+                        stateout, timeman)
 from noahmp_amd.engine import ColumnState, Engine  # noqa: E402
 from noahmp_amd.params import Params  # noqa: E402
 
@@ -207,6 +216,30 @@ def main():
         vc_row = torch.empty(n, dtype=dt, device=dev)
         cases.append(("static_monthly", None,
                       lambda: eng.static_monthly(vc_tab, 5, 6, 1 / 3, vc_row), n * (8 + prec)))
+        # accumulated output and interval extremes: the every-step kernels
+        # behind the step.  The extremes' resident state is primed by one call
+        # with k = 1; the timed calls (k = 2, the same values) set no new extreme
+        acc = torch.zeros((L.NACC, n), dtype=torch.float64, device=dev)
+        frc = torch.as_tensor(rng.normal(size=(L.NFORCING, n)), device=dev).to(dt)
+        cases.append(("accumulate", None, lambda: eng.accumulate(diag, frc, acc, 900.0),
+                      n * (17 * prec + 2 * 17 * 8)))
+        for spec in ("T2M,PRCP,TG,SNEQV",
+                     "FSH,TRAD,T2M,RUNSRF,RUNSUB,ALBEDO,PRCP,SFCTMP,TG,TV,SNEQV,SNOWH,SMC1,"
+                     "SH2O1,STC1,ZWT"):
+            ser = xtr.parse([(x, 15) for x in spec.split(",")])
+            ns = len(ser)
+            kr, masks = xtr.pairs(ser), xtr.masks(ser)
+            xval = torch.zeros((2 * ns, n), dtype=dt, device=dev)
+            xwhen = torch.zeros((2 * ns, n), dtype=torch.int32, device=dev)
+            xout = torch.empty((4 * ns, n), dtype=dt, device=dev)
+            st = so_cs[prec].state
+            eng.extremes_update(kr, 1, xval, xwhen, diag, frc, st)
+            cases += [("extremes_update", f"{ns} series",
+                       lambda kr=kr, xval=xval, xwhen=xwhen, st=st: eng.extremes_update(
+                           kr, 2, xval, xwhen, diag, frc, st), n * ns * 3 * prec),
+                      ("extremes_output", f"{ns} series, 4 stats",
+                       lambda masks=masks, xval=xval, xwhen=xwhen, xout=xout: eng.extremes_output(
+                           masks, 900.0, xval, xwhen, xout), n * ns * (2 * (prec + 4) + 4 * prec))]
         for name, order, fn, nbytes in cases:
             if only and name not in only:
                 continue

@@ -37,6 +37,11 @@ state_out="all" and without, interleaved, reported the same way.
 --veg-clim-runs N times the vegetation fraction's updates instead: the case
 with a seasonal GREENFRAC, N fresh runs each without veg_clim and with
 veg_clim="step", interleaved, reported the same way.
+
+--extremes-runs N times the interval extremes instead: N fresh runs of each of
+--variants (default off,state,diag: without the option, with a spec of state
+and forcing series only, with a spec that has flux series and so writes the
+fluxes every step), interleaved with the order rotated, reported the same way.
 """
 import argparse
 import json
@@ -268,15 +273,62 @@ def veg_clim_runs(a, nml):
             "summary": summary, "driver": [r for v in names for r in runs[v]]}
 
 
+# --extremes-runs: the specs of the two variants with the option on
+EXTREMES_SPECS = {"state": "PRCP:max+tmax,SFCTMP,TG,SNEQV,SMC1,STC1",
+                  "diag": "T2M,TRAD,FSH:max+tmax,RUNSRF:max+tmax,PRCP:max+tmax,TG"}
+
+
+def extremes_runs(a, nml):
+    """Fresh runs without extremes ("off"), with state and forcing series only
+    ("state": the steps between output steps stay at DIAG_NONE) and with flux
+    series ("diag": every step writes its fluxes), interleaved, the order
+    rotated from round to round; ms per step of each run, and each variant's
+    median and range.  "off" alone with --keep-case times this tree on a case
+    written before, next to another tree's runs on the same files."""
+    if not (a.keep_case and os.path.exists(config.Config(nml).constfile)):
+        import make_offline_case
+        make_offline_case.main([nml, "--ny", str(a.ny), "--nx", str(a.nx), "--kind", "mixed"])
+    cfg = config.Config(nml)
+    names = [v for v in a.variants.split(",") if v]
+    runs = {v: [] for v in names}
+    for i in range(a.extremes_runs):
+        for name in names[i % len(names):] + names[:i % len(names)]:
+            kw = {} if name == "off" else dict(extremes=EXTREMES_SPECS[name])
+            r, _, drv = time_driver(cfg, 4, True, a.warm, a.steps, a.threads, "device", True, **kw)
+            r["variant"], r["round"] = name, i
+            r["pcie_down_bytes_per_output_step"] = len(drv.out_names) * 4 * drv.cs.ncol
+            print(json.dumps(r), flush=True)
+            runs[name].append(r)
+            del drv
+    summary = {}
+    for name, rs in runs.items():
+        ms = sorted(r["ms_per_step"] for r in rs)
+        summary[name] = {"runs": len(ms), "median_ms_per_step": float(np.median(ms)),
+                         "min_ms_per_step": ms[0], "max_ms_per_step": ms[-1]}
+        if name != "off":
+            summary[name]["spec"] = EXTREMES_SPECS[name]
+    print(json.dumps(summary), flush=True)
+    return {"case": f"{a.ny} x {a.nx} land points (mixed USGS/STAS columns), 900-s steps, "
+                    "hourly LDASIN, 3-hourly LDASOUT; fp32, file bytes ingested on the device; "
+                    "fresh drivers, variants interleaved, order rotated",
+            "summary": summary, "driver": [r for v in names for r in runs[v]]}
+
+
 def main():
     ap = argparse.ArgumentParser()
+    ap.add_argument("--extremes-runs", type=int, default=0, metavar="N",
+                    help="time N fresh runs each of --variants (off, state, diag: without "
+                         "extremes, with state / forcing series, with flux series), interleaved, "
+                         "instead")
     ap.add_argument("--veg-clim-runs", type=int, default=0, metavar="N",
                     help="time N fresh runs each without veg_clim and with veg_clim='step', "
                          "interleaved, instead")
-    ap.add_argument("--variants", default="off,step", metavar="NAME[,NAME]",
-                    help="with --veg-clim-runs: the variants to time (off, daily, step)")
+    ap.add_argument("--variants", default=None, metavar="NAME[,NAME]",
+                    help="with --veg-clim-runs: the variants to time (off, daily, step; default "
+                         "off,step); with --extremes-runs: off, state, diag (default all three)")
     ap.add_argument("--keep-case", action="store_true",
-                    help="with --veg-clim-runs: reuse the case files in --dir if they exist")
+                    help="with --veg-clim-runs or --extremes-runs: reuse the case files in "
+                         "--dir if they exist")
     ap.add_argument("--state-out-runs", type=int, default=0, metavar="N",
                     help="time N fresh runs each with and without state_out='all', interleaved, "
                          "instead")
@@ -296,9 +348,12 @@ def main():
     a = ap.parse_args()
     os.makedirs(a.dir, exist_ok=True)
     nml = write_namelist(a.dir)
-    if a.interp_runs or a.state_out_runs or a.veg_clim_runs:
+    if a.variants is None:
+        a.variants = "off,state,diag" if a.extremes_runs else "off,step"
+    if a.interp_runs or a.state_out_runs or a.veg_clim_runs or a.extremes_runs:
         res = (interp_runs(a, nml) if a.interp_runs else state_out_runs(a, nml)
-               if a.state_out_runs else veg_clim_runs(a, nml))
+               if a.state_out_runs else veg_clim_runs(a, nml) if a.veg_clim_runs
+               else extremes_runs(a, nml))
         if a.out:
             os.makedirs(os.path.dirname(os.path.abspath(a.out)), exist_ok=True)
             with open(a.out, "w") as f:
