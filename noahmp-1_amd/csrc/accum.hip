@@ -18,8 +18,8 @@
 
 #include <cstdint>
 
-#include "noahmp_engine.h"
-#include "sflx_kargs.h"
+#include "col_math.h"
+#include "engine_impl.h"
 
 namespace nmp {
 
@@ -46,27 +46,11 @@ __global__ __launch_bounds__(256) void accumulate_kernel(int64_t ncol, int64_t l
   }
 }
 
-hipError_t launch_accumulate(int precision, int64_t ncol, int64_t ld, float dt, const void* diag,
-                             const void* forcing, double* acc, hipStream_t stream) {
-  const int64_t grid = (ncol + 255) / 256;
-  if (grid <= 0) return hipSuccess;
-  if (precision == 4)
-    hipLaunchKernelGGL(accumulate_kernel<float>, dim3((unsigned)grid), dim3(256), 0, stream, ncol,
-                       ld, (double)dt, static_cast<const float*>(diag),
-                       static_cast<const float*>(forcing), acc);
-  else
-    hipLaunchKernelGGL(accumulate_kernel<double>, dim3((unsigned)grid), dim3(256), 0, stream, ncol,
-                       ld, (double)dt, static_cast<const double*>(diag),
-                       static_cast<const double*>(forcing), acc);
-  return hipGetLastError();
-}
-
-// The reference's BEG_WB / END_WB (func.f90:339-344, :723-727) in its
-// operation order and in engine precision: canopy water and ice, snow water
-// equivalent, aquifer water, then the four soil layers' total water over
-// their thicknesses DZSNSO (:322-328).  Fortran soil layer IZ is C index
-// IZ + 2 of the 7-layer ZSNSO.  Columns that are not soil (IST != 1) get 0,
-// as the reference sets ERRWAT = 0 for them (:729-730).
+// The reference's BEG_WB / END_WB in engine precision (col_math.h
+// water_storage): canopy water and ice, snow water equivalent, aquifer water,
+// then the four soil layers' total water over their thicknesses.  Columns
+// that are not soil (IST != 1) get 0, as the reference sets ERRWAT = 0 for
+// them (func.f90:729-730).
 template <class T>
 __global__ __launch_bounds__(256) void water_storage_kernel(int64_t ncol, int64_t ld,
                                                             const T* __restrict__ state,
@@ -81,30 +65,19 @@ __global__ __launch_bounds__(256) void water_storage_kernel(int64_t ncol, int64_
   }
   const T* s = state + c;
   const int isn = isnow[c];
-  T w = ((s[NMP_S_CANLIQ * ld] + s[NMP_S_CANICE * ld]) + s[NMP_S_SNEQV * ld]) + s[NMP_S_WA * ld];
+  const T canliq = s[NMP_S_CANLIQ * ld], canice = s[NMP_S_CANICE * ld];
+  const T sneqv = s[NMP_S_SNEQV * ld], wa = s[NMP_S_WA * ld];
+  T z[NMP_NSOIL + 1], smc[NMP_NSOIL], dz[NMP_NSOIL];
+  // ZSNSO's soil rows are C index 2..6; the first, the snow pack's bottom, is
+  // used (and loaded) only under snow
+  z[0] = isn == 0 ? (T)0 : s[(NMP_S_ZSNSO + 2) * ld];
 #pragma unroll
-  for (int iz = 1; iz <= NMP_NSOIL; ++iz) {
-    const T zb = s[(NMP_S_ZSNSO + iz + 2) * ld];
-    const T dz = iz == isn + 1 ? -zb : s[(NMP_S_ZSNSO + iz + 1) * ld] - zb;
-    w = w + (s[(NMP_S_SMC + iz - 1) * ld] * dz) * (T)1000;
+  for (int i = 0; i < NMP_NSOIL; ++i) {
+    z[i + 1] = s[(NMP_S_ZSNSO + 3 + i) * ld];
+    smc[i] = s[(NMP_S_SMC + i) * ld];
   }
-  storage[c] = w;
-}
-
-hipError_t launch_water_storage(int precision, int64_t ncol, int64_t ld, const void* state,
-                                const int32_t* isnow, const int32_t* static_i, void* storage,
-                                hipStream_t stream) {
-  const int64_t grid = (ncol + 255) / 256;
-  if (grid == 0) return hipSuccess;
-  if (precision == 4)
-    hipLaunchKernelGGL(water_storage_kernel<float>, dim3((unsigned)grid), dim3(256), 0, stream,
-                       ncol, ld, static_cast<const float*>(state), isnow, static_i,
-                       static_cast<float*>(storage));
-  else
-    hipLaunchKernelGGL(water_storage_kernel<double>, dim3((unsigned)grid), dim3(256), 0, stream,
-                       ncol, ld, static_cast<const double*>(state), isnow, static_i,
-                       static_cast<double*>(storage));
-  return hipGetLastError();
+  soil_thickness(z, isn, dz);
+  storage[c] = water_storage(canliq, canice, sneqv, wa, smc, dz);
 }
 
 // The interval's NMP_B_* block from the accumulators: time means of the
@@ -148,20 +121,41 @@ __global__ __launch_bounds__(256) void accum_finish_kernel(int64_t ncol, int64_t
   stor_beg[c] = end;
 }
 
-hipError_t launch_accum_finish(int precision, int64_t ncol, int64_t ld, double span_s, double* acc,
-                               const void* stor_end, void* stor_beg, void* out,
-                               hipStream_t stream) {
-  const int64_t grid = (ncol + 255) / 256;
-  if (grid == 0) return hipSuccess;
-  if (precision == 4)
-    hipLaunchKernelGGL(accum_finish_kernel<float>, dim3((unsigned)grid), dim3(256), 0, stream,
-                       ncol, ld, span_s, acc, static_cast<const float*>(stor_end),
-                       static_cast<float*>(stor_beg), static_cast<float*>(out));
-  else
-    hipLaunchKernelGGL(accum_finish_kernel<double>, dim3((unsigned)grid), dim3(256), 0, stream,
-                       ncol, ld, span_s, acc, static_cast<const double*>(stor_end),
-                       static_cast<double*>(stor_beg), static_cast<double*>(out));
-  return hipGetLastError();
+}  // namespace nmp
+
+extern "C" {
+
+int nmp_accumulate(nmp_engine* eng, int64_t ncol, int64_t ld, float dt, const void* diag,
+                   const void* forcing, double* acc, void* stream) {
+  if (!eng || ncol < 0 || nmp::bad_ld(ld, ncol)) return NMP_E_ARG;
+  if (ncol == 0) return NMP_OK;
+  if (!diag || !forcing || !acc) return NMP_E_ARG;
+  if (int rc = nmp::ensure_device(eng->device)) return rc;
+  return nmp::launch_cols(eng->precision, ncol, stream, nmp::accumulate_kernel<float>,
+                          nmp::accumulate_kernel<double>, ncol, ld, dt, diag, forcing, acc);
 }
 
-}  // namespace nmp
+int nmp_water_storage(nmp_engine* eng, int64_t ncol, int64_t ld, const void* state,
+                      const int32_t* isnow, const int32_t* static_i, void* storage, void* stream) {
+  if (!eng || ncol < 0 || nmp::bad_ld(ld, ncol)) return NMP_E_ARG;
+  if (ncol == 0) return NMP_OK;
+  if (!state || !isnow || !static_i || !storage) return NMP_E_ARG;
+  if (int rc = nmp::ensure_device(eng->device)) return rc;
+  return nmp::launch_cols(eng->precision, ncol, stream, nmp::water_storage_kernel<float>,
+                          nmp::water_storage_kernel<double>, ncol, ld, state, isnow, static_i,
+                          storage);
+}
+
+int nmp_accum_finish(nmp_engine* eng, int64_t ncol, int64_t ld, double span_s, double* acc,
+                     const void* stor_end, void* stor_beg, void* out, void* stream) {
+  // !(span_s > 0) also refuses NaN
+  if (!eng || ncol < 0 || nmp::bad_ld(ld, ncol) || !(span_s > 0.0)) return NMP_E_ARG;
+  if (ncol == 0) return NMP_OK;
+  if (!acc || !stor_end || !stor_beg || !out) return NMP_E_ARG;
+  if (int rc = nmp::ensure_device(eng->device)) return rc;
+  return nmp::launch_cols(eng->precision, ncol, stream, nmp::accum_finish_kernel<float>,
+                          nmp::accum_finish_kernel<double>, ncol, ld, span_s, acc, stor_end,
+                          stor_beg, out);
+}
+
+}  // extern "C"

@@ -18,24 +18,21 @@
 // nmp_drift_reduce: per group the largest drift and where, the count of
 // columns over the tolerance and the weighted sum, over the rank's whole
 // block.  The sum's tree is fixed by the interface (include/noahmp_engine.h
-// "Spin-up drift"), there are no atomics and no completion flags, and every
-// operation is one IEEE double operation, so a host reproduces every bit:
-//
-//   pass 1  one wavefront per chunk of NMP_DRIFT_CHUNK = 256 columns; lane l
-//           adds, from +0.0 and in this order, the rounded products
-//           (double)d * w of columns 256 k + l + 64 j, j = 0..3 (a column
-//           >= ncol or of weight 0 is left out: not loaded, not multiplied);
-//           then the xor butterfly x = x + shfl_xor(x, s), s = 32 .. 1.
-//   pass 2  from +0.0, the chunk partials added in chunk order.
+// "Spin-up drift"; its pieces are col_math.h's), there are no atomics and no
+// completion flags, and every operation is one IEEE double operation, so a
+// host reproduces every bit.  The terms of pass 1 are the rounded products
+// (double)d * w of columns 256 k + l + 64 j, j = 0..3 (a column >= ncol or of
+// weight 0 is left out: not loaded, not multiplied).
 //
 // max, arg and count do not depend on the order they are combined in; the
 // lanes and chunks combine them by the same butterfly and a strided loop.
 #include <hip/hip_runtime.h>
 
 #include <cstdint>
+#include <mutex>
 
-#include "noahmp_engine.h"
-#include "sflx_kargs.h"
+#include "col_math.h"
+#include "engine_impl.h"
 
 namespace nmp {
 
@@ -51,16 +48,16 @@ __global__ __launch_bounds__(256) void state_drift_kernel(int64_t ncol, int64_t 
   if (c >= ncol) return;
   const T* s = state + c;
   auto ld1 = [&](int row) { return __builtin_nontemporal_load(s + row * ld); };
-  T v[NMP_NTRACKED];
+  T v[NMP_NTRACKED], smc[NMP_NSOIL];
 #pragma unroll
-  for (int i = 0; i < NMP_NSOIL; ++i) v[NMP_K_SMC + i] = ld1(NMP_S_SMC + i);
+  for (int i = 0; i < NMP_NSOIL; ++i) v[NMP_K_SMC + i] = smc[i] = ld1(NMP_S_SMC + i);
 #pragma unroll
   for (int i = 0; i < NMP_NSOIL; ++i) v[NMP_K_STC + i] = ld1(NMP_S_STC + NMP_NSNOW + i);
   v[NMP_K_SNEQV] = ld1(NMP_S_SNEQV);
   v[NMP_K_WA] = ld1(NMP_S_WA);
   v[NMP_K_ZWT] = ld1(NMP_S_ZWT);
-  // TWS: water_storage_kernel's expression; ZSNSO's soil rows are C index 2..6
-  T z[NMP_NSOIL + 1];
+  // TWS: ZSNSO's soil rows are C index 2..6
+  T z[NMP_NSOIL + 1], dz[NMP_NSOIL];
 #pragma unroll
   for (int i = 0; i <= NMP_NSOIL; ++i) z[i] = ld1(NMP_S_ZSNSO + 2 + i);
   const T canliq = ld1(NMP_S_CANLIQ), canice = ld1(NMP_S_CANICE);
@@ -70,13 +67,8 @@ __global__ __launch_bounds__(256) void state_drift_kernel(int64_t ncol, int64_t 
 #pragma unroll
   for (int i = 0; i < 6; ++i) pool[i] = ld1(NMP_S_LFMASS + i);
 
-  T w = ((canliq + canice) + v[NMP_K_SNEQV]) + v[NMP_K_WA];
-#pragma unroll
-  for (int iz = 1; iz <= NMP_NSOIL; ++iz) {
-    const T zb = z[iz];
-    const T dz = iz == isn + 1 ? -zb : z[iz - 1] - zb;
-    w = w + (v[NMP_K_SMC + iz - 1] * dz) * (T)1000;
-  }
+  soil_thickness(z, isn, dz);
+  const T w = water_storage(canliq, canice, v[NMP_K_SNEQV], v[NMP_K_WA], smc, dz);
   v[NMP_K_TWS] = ist == 1 ? w : (T)0;
   v[NMP_K_CTOT] = ((((pool[0] + pool[1]) + pool[2]) + pool[3]) + pool[4]) + pool[5];
 
@@ -108,29 +100,9 @@ __global__ __launch_bounds__(256) void state_drift_kernel(int64_t ncol, int64_t 
   for (int k = 0; k < NMP_NTRACKED; ++k) sn[k * ld_snap] = v[k];
 }
 
-hipError_t launch_state_drift(int precision, int64_t ncol, int64_t ld, const void* state,
-                              const int32_t* isnow, const int32_t* static_i, void* snap,
-                              int64_t ld_snap, void* drift, int64_t ld_drift,
-                              hipStream_t stream) {
-  const int64_t grid = (ncol + 255) / 256;
-  if (grid == 0) return hipSuccess;
-  if (precision == 4)
-    hipLaunchKernelGGL(state_drift_kernel<float>, dim3((unsigned)grid), dim3(256), 0, stream,
-                       ncol, ld, static_cast<const float*>(state), isnow, static_i,
-                       static_cast<float*>(snap), ld_snap, static_cast<float*>(drift), ld_drift);
-  else
-    hipLaunchKernelGGL(state_drift_kernel<double>, dim3((unsigned)grid), dim3(256), 0, stream,
-                       ncol, ld, static_cast<const double*>(state), isnow, static_i,
-                       static_cast<double*>(snap), ld_snap, static_cast<double*>(drift),
-                       ld_drift);
-  return hipGetLastError();
-}
-
 namespace {
 
-constexpr int kWave = 64;
-constexpr int kPerLane = NMP_DRIFT_CHUNK / kWave;  // 4 columns per lane
-constexpr int kWavesPerBlock = 4;
+static_assert(NMP_DRIFT_CHUNK == kWave * kPerLane, "one wavefront per chunk");
 constexpr int kNG = NMP_NDRIFT;
 
 // rows of the pass-1 scratch, each nchunk 8-byte words: the 7 weighted sums
@@ -154,14 +126,7 @@ __device__ __forceinline__ void better(double& m, int64_t& a, double m2, int64_t
   }
 }
 
-__device__ __forceinline__ int64_t shfl_xor_i64(int64_t x, int s) {
-  return (int64_t)__shfl_xor((long long)x, s, kWave);
-}
-
-// FULL: no column of the chunk is left out, so loads and adds carry no
-// predicate -- the same operations in the same order; with predicates the
-// compiler branches around every load and waits for each (regions.hip
-// measured 2.3x the time in fp32).
+// FULL: no column of the chunk is left out (col_math.h chunk_full)
 template <class T, bool FULL>
 __device__ __forceinline__ void reduce_chunk(const T* __restrict__ drift, int64_t ld_drift,
                                              const int64_t (&col)[kPerLane],
@@ -196,9 +161,9 @@ __device__ __forceinline__ void reduce_chunk(const T* __restrict__ drift, int64_
         better(m, a, d, col[j]);
         n += !(d <= t);
       }
+    x = wave_sum(x);
 #pragma unroll
     for (int s = kWave / 2; s >= 1; s >>= 1) {
-      x = x + __shfl_xor(x, s, kWave);
       better(m, a, __shfl_xor(m, s, kWave), shfl_xor_i64(a, s));
       n += shfl_xor_i64(n, s);
     }
@@ -213,8 +178,7 @@ __device__ __forceinline__ void reduce_chunk(const T* __restrict__ drift, int64_
 #pragma unroll
   for (int j = 0; j < kPerLane; ++j)
     if (FULL || ok[j]) x = x + w[j];
-#pragma unroll
-  for (int s = kWave / 2; s >= 1; s >>= 1) x = x + __shfl_xor(x, s, kWave);
+  x = wave_sum(x);
   if (lane == 0) part[(kRowSum + kNG) * nchunk] = x;
 }
 
@@ -240,19 +204,15 @@ __global__ __launch_bounds__(kWave* kWavesPerBlock) void drift_pass1_kernel(
     }
   }
   double* part = partial + k;
-  // wave-uniform: no lane of this chunk leaves a column out
-  if (__all(ok[0] && ok[1] && ok[2] && ok[3]))
+  if (chunk_full(ok))
     reduce_chunk<T, true>(drift, ld_drift, col, ok, w, tol, lane, part, nchunk);
   else
     reduce_chunk<T, false>(drift, ld_drift, col, ok, w, tol, lane, part, nchunk);
 }
 
 // One wavefront per output.  Waves 0..7: the sum of row t of the partials
-// (the 7 weighted sums, then the weights'), from +0.0 in chunk order -- the
-// lanes load 64 consecutive partials at once, the next 64 while these are
-// added, and every lane adds them in order from the lanes' registers
-// (region_pass2_wave_kernel's sequence).  Waves 8..14: group t - 8's max, arg
-// and count, the lanes striding over the chunks.
+// (the 7 weighted sums, then the weights'), from +0.0 in chunk order.  Waves
+// 8..14: group t - 8's max, arg and count, the lanes striding over the chunks.
 __global__ __launch_bounds__(kWave* kWavesPerBlock) void drift_pass2_kernel(
     int64_t nchunk, const double* __restrict__ partial, double* __restrict__ out_max,
     int64_t* __restrict__ out_arg, double* __restrict__ out_wsum, int64_t* __restrict__ out_count,
@@ -261,19 +221,8 @@ __global__ __launch_bounds__(kWave* kWavesPerBlock) void drift_pass2_kernel(
   const int t = blockIdx.x * kWavesPerBlock + threadIdx.x / kWave;
   if (t > 2 * kNG) return;
   if (t <= kNG) {
-    const double* p = partial + (int64_t)(kRowSum + t) * nchunk;
-    double sum = 0.0;
-    double v = lane < nchunk ? p[lane] : 0.0;
-    for (int64_t k = 0; k < nchunk; k += kWave) {
-      const double next = k + kWave + lane < nchunk ? p[k + kWave + lane] : 0.0;
-      // lane i's partial to every lane (i is uniform: two v_readlane_b32)
-      const int lo = __double2loint(v), hi = __double2hiint(v);
-      const int m = nchunk - k >= kWave ? kWave : (int)(nchunk - k);
-      for (int i = 0; i < m; ++i)
-        sum = sum + __hiloint2double(__builtin_amdgcn_readlane(hi, i),
-                                     __builtin_amdgcn_readlane(lo, i));
-      v = next;
-    }
+    const double sum =
+        wave_ordered_sum(partial + (int64_t)(kRowSum + t) * nchunk, 0, nchunk, lane);
     if (lane == 0) {
       if (t < kNG)
         out_wsum[t] = sum;
@@ -307,30 +256,55 @@ __global__ __launch_bounds__(kWave* kWavesPerBlock) void drift_pass2_kernel(
 
 }  // namespace
 
-hipError_t launch_drift_reduce(int precision, int64_t ncol, int64_t ld_drift, const void* drift,
-                               const double* weight, const double* tol, void* partial,
-                               double* out_max, int64_t* out_arg, double* out_wsum,
-                               int64_t* out_count, double* out_wtot, hipStream_t stream) {
+}  // namespace nmp
+
+extern "C" {
+
+int nmp_state_drift(nmp_engine* eng, int64_t ncol, int64_t ld, const void* state,
+                    const int32_t* isnow, const int32_t* static_i, void* snap, int64_t ld_snap,
+                    void* drift, int64_t ld_drift, void* stream) {
+  if (!eng || ncol < 0 || nmp::bad_ld(ld, ncol) || nmp::bad_ld(ld_snap, ncol) ||
+      (drift && nmp::bad_ld(ld_drift, ncol)))
+    return NMP_E_ARG;
+  if (ncol == 0) return NMP_OK;
+  if (!state || !isnow || !static_i || !snap) return NMP_E_ARG;
+  if (int rc = nmp::ensure_device(eng->device)) return rc;
+  std::lock_guard<std::mutex> lk(eng->host_mu);
+  return nmp::launch_cols(eng->precision, ncol, stream, nmp::state_drift_kernel<float>,
+                          nmp::state_drift_kernel<double>, ncol, ld, state, isnow, static_i, snap,
+                          ld_snap, drift, ld_drift);
+}
+
+int nmp_drift_reduce(nmp_engine* eng, int64_t ncol, int64_t ld_drift, const void* drift,
+                     const double* weight, const double* tol, void* partial, double* out_max,
+                     int64_t* out_arg, double* out_wsum, int64_t* out_count, double* out_wtot,
+                     void* stream) {
+  using namespace nmp;
+  if (!eng || ncol < 0 || bad_ld(ld_drift, ncol)) return NMP_E_ARG;
+  if (!drift || !tol || !partial || !out_max || !out_arg || !out_wsum || !out_count || !out_wtot)
+    return NMP_E_ARG;
+  if (int rc = ensure_device(eng->device)) return rc;
+  // the two passes of one call are enqueued back to back
+  std::lock_guard<std::mutex> lk(eng->host_mu);
+  const hipStream_t st = static_cast<hipStream_t>(stream);
   const int64_t nchunk = (ncol + NMP_DRIFT_CHUNK - 1) / NMP_DRIFT_CHUNK;
   double* part = static_cast<double*>(partial);
+  const dim3 block(kWave * kWavesPerBlock);
   if (nchunk > 0) {
-    const int64_t grid1 = (nchunk + kWavesPerBlock - 1) / kWavesPerBlock;
-    if (precision == 4)
-      hipLaunchKernelGGL(drift_pass1_kernel<float>, dim3((unsigned)grid1),
-                         dim3(kWave * kWavesPerBlock), 0, stream, ncol, ld_drift,
+    const dim3 grid1((unsigned)((nchunk + kWavesPerBlock - 1) / kWavesPerBlock));
+    if (eng->precision == 4)
+      hipLaunchKernelGGL(drift_pass1_kernel<float>, grid1, block, 0, st, ncol, ld_drift,
                          static_cast<const float*>(drift), weight, tol, nchunk, part);
     else
-      hipLaunchKernelGGL(drift_pass1_kernel<double>, dim3((unsigned)grid1),
-                         dim3(kWave * kWavesPerBlock), 0, stream, ncol, ld_drift,
+      hipLaunchKernelGGL(drift_pass1_kernel<double>, grid1, block, 0, st, ncol, ld_drift,
                          static_cast<const double*>(drift), weight, tol, nchunk, part);
-    hipError_t e = hipGetLastError();
-    if (e != hipSuccess) return e;
+    if (int rc = rc_of(hipGetLastError())) return rc;
   }
   // without a column pass 2 alone writes the empty result
   const int grid2 = (2 * kNG + 1 + kWavesPerBlock - 1) / kWavesPerBlock;
-  hipLaunchKernelGGL(drift_pass2_kernel, dim3(grid2), dim3(kWave * kWavesPerBlock), 0, stream,
-                     nchunk, part, out_max, out_arg, out_wsum, out_count, out_wtot);
-  return hipGetLastError();
+  hipLaunchKernelGGL(drift_pass2_kernel, dim3(grid2), block, 0, st, nchunk, part, out_max, out_arg,
+                     out_wsum, out_count, out_wtot);
+  return rc_of(hipGetLastError());
 }
 
-}  // namespace nmp
+}  // extern "C"

@@ -5,6 +5,10 @@
 // only the device copy of the lookup tables; every per-column array is
 // caller-owned device memory (SoA), so state stays resident in HBM across
 // steps and the caller decides streams, graphs and sharding.
+//
+// Here: the engine's lifecycle and option setters, the step entries, the
+// synchronous host entries and nmp_state_from_aos.  Every per-column helper
+// entry lives in the file of its kernel (engine_impl.h).
 #include <hip/hip_runtime.h>
 
 #include <cmath>
@@ -15,41 +19,13 @@
 #include <new>
 #include <vector>
 
-#include "dev_params.h"
-#include "noahmp_engine.h"
-
+#include "engine_impl.h"
 #include "sflx_kargs.h"
 
-struct nmp_engine {
-  int device;
-  int precision;
-  int math;  // 0 = reference-rounded transcendentals (parity), 1 = fast (fp32 only)
-  int cpw;   // columns per wave: 8..64, or 0 = chosen per launch from ncol
-  int simds; // SIMDs on the device (CUs x 4)
-  int os;    // compiled option set matching opts (sflx_kernel.hip kOptionSet), 0 = none
-  int variant;  // NMP_LAUNCH_AUTO | SMALL | FULL: occupancy instantiation per launch
-  nmp_options opts;
-  nmp::DevParams* dparams;
-  // the synchronous host entries (nmp_sflx_columns, nmp_*_host): a private
-  // non-blocking stream, so they neither wait for nor stall the caller's
-  // streams, and device scratch kept across calls (grown on demand), so a
-  // scalar call from a Fortran loop pays no allocation
-  hipStream_t hstream;
-  char* scratch;
-  size_t scratch_bytes;
-  // the host entries share hstream and scratch: one at a time per engine
-  // (two threads calling them on one engine are serialized here)
-  std::mutex host_mu;
-};
+using nmp::ensure_device;
+using nmp::kMaxColumns;
 
 namespace {
-
-// largest column stride: the kernels form a column's byte offset from a
-// field's base in 32 bits (2^29 columns of 8-byte fp64 values = 4 GiB)
-constexpr int64_t kMaxColumns = int64_t(1) << 29;
-// most fields one nmp_region_reduce call takes (its launches count
-// nreg x nfield threads in 64 bits and blocks in 32)
-constexpr int kMaxRegionFields = 1024;
 
 bool options_ok(const nmp_options& o) {
   // valid values of each option (core/module_noahmp_global.f90:17-74)
@@ -69,13 +45,6 @@ int option_set(const nmp_options& o) {
                     o.opt_snf == 1 && o.opt_tbot == 1 && o.opt_stc == 1;
   if (!rest) return 0;
   return o.opt_veg == 1 ? 1 : o.opt_veg == 2 ? 2 : 0;
-}
-
-int ensure_device(int dev) {
-  int cur = -1;
-  if (hipGetDevice(&cur) != hipSuccess) return NMP_E_DEVICE;
-  if (cur != dev && hipSetDevice(dev) != hipSuccess) return NMP_E_DEVICE;
-  return NMP_OK;
 }
 
 // Device scratch of at least nb bytes for a synchronous host entry (the
@@ -357,218 +326,6 @@ int nmp_step_binned(nmp_engine* eng, int64_t ncol, int64_t ld, const float zsoil
   return launch(eng, ncol, ld, zsoil, dt, julian, yearlen, state, isnow, static_f, static_i,
                 forcing, diag, diag_level, col_status, static_cast<hipStream_t>(stream), order,
                 cost);
-}
-
-int nmp_rebin(nmp_engine* eng, int64_t ncol, const uint8_t* cost, int32_t* order, int32_t tile,
-              void* stream) {
-  if (!eng || ncol < 0 || !cost || !order || ncol > INT32_MAX) return NMP_E_ARG;
-  if (tile < 64 || tile > (1 << 20) || tile % 64 != 0) return NMP_E_ARG;
-  if (ncol == 0) return NMP_OK;
-  if (ensure_device(eng->device) != NMP_OK) return NMP_E_DEVICE;
-  return nmp::launch_rebin(cost, order, ncol, tile, static_cast<hipStream_t>(stream)) ==
-                 hipSuccess
-             ? NMP_OK
-             : NMP_E_DEVICE;
-}
-
-int nmp_forcing_synth(nmp_engine* eng, int64_t ncol, int64_t ld, const void* climate,
-                      double julian, int32_t yearlen, uint64_t seed, int64_t step,
-                      int64_t first_col, void* forcing, void* stream) {
-  if (!eng || ncol < 0 || ld < ncol || yearlen <= 0 || step < 0 || first_col < 0) return NMP_E_ARG;
-  if (ncol == 0) return NMP_OK;
-  if (!climate || !forcing) return NMP_E_ARG;
-  if (ensure_device(eng->device) != NMP_OK) return NMP_E_DEVICE;
-  return nmp::launch_forcing_synth(eng->precision, ncol, ld, climate, julian, yearlen, seed, step,
-                                   first_col, forcing, static_cast<hipStream_t>(stream)) ==
-                 hipSuccess
-             ? NMP_OK
-             : NMP_E_DEVICE;
-}
-
-int nmp_forcing_from_ldasin(nmp_engine* eng, int64_t ncol, int64_t ld, const float* ldasin,
-                            void* forcing, void* stream) {
-  if (!eng || ncol < 0 || ld < ncol || ld >= kMaxColumns) return NMP_E_ARG;
-  if (ncol == 0) return NMP_OK;
-  if (!ldasin || !forcing) return NMP_E_ARG;
-  if (ensure_device(eng->device) != NMP_OK) return NMP_E_DEVICE;
-  return nmp::launch_forcing_ldasin(eng->precision, ncol, ld, ldasin, nullptr, 0.0, 0.0, 0.0,
-                                    forcing, static_cast<hipStream_t>(stream)) == hipSuccess
-             ? NMP_OK
-             : NMP_E_DEVICE;
-}
-
-int nmp_ldasin_ingest(nmp_engine* eng, int64_t ncol, int64_t ld, int64_t npts,
-                      const void* grid_be, const int32_t* point, float* ldasin, void* stream) {
-  if (!eng || ncol < 0 || ld < ncol || ld >= kMaxColumns || npts < 0 || npts >= kMaxColumns)
-    return NMP_E_ARG;
-  if (ncol == 0) return NMP_OK;
-  if (!grid_be || !point || !ldasin || npts == 0) return NMP_E_ARG;
-  if (ensure_device(eng->device) != NMP_OK) return NMP_E_DEVICE;
-  return nmp::launch_ldasin_ingest(ncol, ld, npts, grid_be, point, ldasin,
-                                   static_cast<hipStream_t>(stream)) == hipSuccess
-             ? NMP_OK
-             : NMP_E_DEVICE;
-}
-
-int nmp_ldasin_regrid(nmp_engine* eng, int64_t ncol, int64_t ld, int64_t npts,
-                      const void* grid_be, const int32_t* corner, const double* weight,
-                      uint32_t nearest_mask, float* ldasin, void* stream) {
-  if (!eng || ncol < 0 || ld < ncol || ld >= kMaxColumns || npts < 1 || npts >= kMaxColumns)
-    return NMP_E_ARG;
-  if (ncol == 0) return NMP_OK;
-  if (!grid_be || !corner || !weight || !ldasin) return NMP_E_ARG;
-  if (ensure_device(eng->device) != NMP_OK) return NMP_E_DEVICE;
-  return nmp::launch_ldasin_regrid(ncol, ld, npts, grid_be, corner, weight, nearest_mask, ldasin,
-                                   static_cast<hipStream_t>(stream)) == hipSuccess
-             ? NMP_OK
-             : NMP_E_DEVICE;
-}
-
-int nmp_ldasin_downscale(nmp_engine* eng, int64_t ncol, int64_t ld, const float* dz, double lapse,
-                         float* ldasin, void* stream) {
-  if (!eng || ncol < 0 || ld < ncol || ld >= kMaxColumns) return NMP_E_ARG;
-  if (ncol == 0) return NMP_OK;
-  if (!dz || !ldasin) return NMP_E_ARG;
-  if (ensure_device(eng->device) != NMP_OK) return NMP_E_DEVICE;
-  return nmp::launch_ldasin_downscale(ncol, ld, dz, lapse, ldasin,
-                                      static_cast<hipStream_t>(stream)) == hipSuccess
-             ? NMP_OK
-             : NMP_E_DEVICE;
-}
-
-int nmp_ldasout_grid(nmp_engine* eng, int64_t ncol, int64_t ld, int64_t npts, int nfield,
-                     const void* diag, const int32_t* point, double fill, void* grid_be,
-                     void* stream) {
-  if (!eng || ncol < 0 || ld < ncol || ld >= kMaxColumns || npts < 0 || npts >= kMaxColumns ||
-      nfield < 0 || nfield > NMP_NDIAG_FULL)
-    return NMP_E_ARG;
-  if (npts == 0 || nfield == 0) return NMP_OK;
-  if (!grid_be || (ncol > 0 && (!diag || !point))) return NMP_E_ARG;
-  if (ensure_device(eng->device) != NMP_OK) return NMP_E_DEVICE;
-  return nmp::launch_ldasout_grid(eng->precision, ncol, ld, npts, nfield, diag, point, fill,
-                                  grid_be, static_cast<hipStream_t>(stream)) == hipSuccess
-             ? NMP_OK
-             : NMP_E_DEVICE;
-}
-
-int nmp_accumulate(nmp_engine* eng, int64_t ncol, int64_t ld, float dt, const void* diag,
-                   const void* forcing, double* acc, void* stream) {
-  if (!eng || ncol < 0 || ld < ncol || ld >= kMaxColumns) return NMP_E_ARG;
-  if (ncol == 0) return NMP_OK;
-  if (!diag || !forcing || !acc) return NMP_E_ARG;
-  if (ensure_device(eng->device) != NMP_OK) return NMP_E_DEVICE;
-  return nmp::launch_accumulate(eng->precision, ncol, ld, dt, diag, forcing, acc,
-                                static_cast<hipStream_t>(stream)) == hipSuccess
-             ? NMP_OK
-             : NMP_E_DEVICE;
-}
-
-int nmp_water_storage(nmp_engine* eng, int64_t ncol, int64_t ld, const void* state,
-                      const int32_t* isnow, const int32_t* static_i, void* storage, void* stream) {
-  if (!eng || ncol < 0 || ld < ncol || ld >= kMaxColumns) return NMP_E_ARG;
-  if (ncol == 0) return NMP_OK;
-  if (!state || !isnow || !static_i || !storage) return NMP_E_ARG;
-  if (ensure_device(eng->device) != NMP_OK) return NMP_E_DEVICE;
-  return nmp::launch_water_storage(eng->precision, ncol, ld, state, isnow, static_i, storage,
-                                   static_cast<hipStream_t>(stream)) == hipSuccess
-             ? NMP_OK
-             : NMP_E_DEVICE;
-}
-
-int nmp_accum_finish(nmp_engine* eng, int64_t ncol, int64_t ld, double span_s, double* acc,
-                     const void* stor_end, void* stor_beg, void* out, void* stream) {
-  // !(span_s > 0) also refuses NaN
-  if (!eng || ncol < 0 || ld < ncol || ld >= kMaxColumns || !(span_s > 0.0)) return NMP_E_ARG;
-  if (ncol == 0) return NMP_OK;
-  if (!acc || !stor_end || !stor_beg || !out) return NMP_E_ARG;
-  if (ensure_device(eng->device) != NMP_OK) return NMP_E_DEVICE;
-  return nmp::launch_accum_finish(eng->precision, ncol, ld, span_s, acc, stor_end, stor_beg, out,
-                                  static_cast<hipStream_t>(stream)) == hipSuccess
-             ? NMP_OK
-             : NMP_E_DEVICE;
-}
-
-int nmp_region_reduce(nmp_engine* eng, int64_t ncol, int64_t ld, int nfield, const void* fields,
-                      int64_t nchunk, const int32_t* entry_col, const double* entry_w,
-                      int64_t nreg, const int64_t* region_chunk0, const double* wsum,
-                      double* partial, double* sums, double* means, void* stream) {
-  if (!eng || ncol < 0 || ld < ncol || ld >= kMaxColumns || nfield < 1 ||
-      nfield > kMaxRegionFields || nchunk < 0 || nchunk >= kMaxColumns || nreg < 0 ||
-      nreg >= kMaxColumns || nreg * nfield / 256 >= INT32_MAX)
-    return NMP_E_ARG;
-  if (nchunk == 0 || nreg == 0) return NMP_OK;
-  if (!fields || !entry_col || !entry_w || !region_chunk0 || !wsum || !partial || !sums)
-    return NMP_E_ARG;
-  if (ensure_device(eng->device) != NMP_OK) return NMP_E_DEVICE;
-  // the two passes of one call are enqueued back to back
-  std::lock_guard<std::mutex> lk(eng->host_mu);
-  return nmp::launch_region_reduce(eng->precision, ncol, ld, nfield, fields, nchunk, entry_col,
-                                   entry_w, nreg, region_chunk0, wsum, partial, sums, means,
-                                   static_cast<hipStream_t>(stream)) == hipSuccess
-             ? NMP_OK
-             : NMP_E_DEVICE;
-}
-
-int nmp_state_output(nmp_engine* eng, int64_t ncol, int64_t ld, const void* state,
-                     const int32_t* isnow, const int32_t* static_i, uint32_t groups,
-                     double fill, void* out, int64_t ld_out, void* stream) {
-  if (!eng || ncol < 0 || ld < ncol || ld >= kMaxColumns || ld_out < ncol ||
-      ld_out >= kMaxColumns || groups == 0 || (groups >> NMP_NXGROUP) != 0)
-    return NMP_E_ARG;
-  if (ncol == 0) return NMP_OK;
-  if (!state || !isnow || !static_i || !out) return NMP_E_ARG;
-  if (ensure_device(eng->device) != NMP_OK) return NMP_E_DEVICE;
-  return nmp::launch_state_output(eng->precision, eng->dparams, ncol, ld, state, isnow, static_i,
-                                  groups, fill, out, ld_out,
-                                  static_cast<hipStream_t>(stream)) == hipSuccess
-             ? NMP_OK
-             : NMP_E_DEVICE;
-}
-
-int nmp_state_drift(nmp_engine* eng, int64_t ncol, int64_t ld, const void* state,
-                    const int32_t* isnow, const int32_t* static_i, void* snap, int64_t ld_snap,
-                    void* drift, int64_t ld_drift, void* stream) {
-  if (!eng || ncol < 0 || ld < ncol || ld >= kMaxColumns || ld_snap < ncol ||
-      ld_snap >= kMaxColumns || (drift && (ld_drift < ncol || ld_drift >= kMaxColumns)))
-    return NMP_E_ARG;
-  if (ncol == 0) return NMP_OK;
-  if (!state || !isnow || !static_i || !snap) return NMP_E_ARG;
-  if (ensure_device(eng->device) != NMP_OK) return NMP_E_DEVICE;
-  std::lock_guard<std::mutex> lk(eng->host_mu);
-  return nmp::launch_state_drift(eng->precision, ncol, ld, state, isnow, static_i, snap, ld_snap,
-                                 drift, ld_drift, static_cast<hipStream_t>(stream)) == hipSuccess
-             ? NMP_OK
-             : NMP_E_DEVICE;
-}
-
-int nmp_drift_reduce(nmp_engine* eng, int64_t ncol, int64_t ld_drift, const void* drift,
-                     const double* weight, const double* tol, void* partial, double* out_max,
-                     int64_t* out_arg, double* out_wsum, int64_t* out_count, double* out_wtot,
-                     void* stream) {
-  if (!eng || ncol < 0 || ld_drift < ncol || ld_drift >= kMaxColumns) return NMP_E_ARG;
-  if (!drift || !tol || !partial || !out_max || !out_arg || !out_wsum || !out_count || !out_wtot)
-    return NMP_E_ARG;
-  if (ensure_device(eng->device) != NMP_OK) return NMP_E_DEVICE;
-  // the two passes of one call are enqueued back to back
-  std::lock_guard<std::mutex> lk(eng->host_mu);
-  return nmp::launch_drift_reduce(eng->precision, ncol, ld_drift, drift, weight, tol, partial,
-                                  out_max, out_arg, out_wsum, out_count, out_wtot,
-                                  static_cast<hipStream_t>(stream)) == hipSuccess
-             ? NMP_OK
-             : NMP_E_DEVICE;
-}
-
-int nmp_forcing_from_ldasin_geo(nmp_engine* eng, int64_t ncol, int64_t ld, const float* ldasin,
-                                const double* geo, double sin_decl, double cos_decl, double ha0,
-                                void* forcing, void* stream) {
-  if (!eng || ncol < 0 || ld < ncol || ld >= kMaxColumns) return NMP_E_ARG;
-  if (ncol == 0) return NMP_OK;
-  if (!ldasin || !geo || !forcing) return NMP_E_ARG;
-  if (ensure_device(eng->device) != NMP_OK) return NMP_E_DEVICE;
-  return nmp::launch_forcing_ldasin(eng->precision, ncol, ld, ldasin, geo, sin_decl, cos_decl, ha0,
-                                    forcing, static_cast<hipStream_t>(stream)) == hipSuccess
-             ? NMP_OK
-             : NMP_E_DEVICE;
 }
 
 int nmp_run(nmp_engine* eng, int64_t ncol, int64_t ld, const float zsoil[4], float dt,

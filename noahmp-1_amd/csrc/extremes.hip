@@ -21,14 +21,11 @@
 #include <cmath>
 #include <cstdint>
 
-#include "noahmp_engine.h"
+#include "engine_impl.h"
 
 namespace nmp {
 
 namespace {
-
-// as engine.hip's: a column's byte offset is formed in 32 bits
-constexpr int64_t kMaxColumns = int64_t(1) << 29;
 
 // by-value kernel argument: word s is kind << 8 | row of series s (update) or
 // the stat mask of series s (output)
@@ -120,22 +117,6 @@ __global__ __launch_bounds__(256) void extremes_output_kernel(int64_t ncol, int 
   }
 }
 
-namespace {
-
-bool bad_ld(int64_t ld, int64_t ncol) { return ld < ncol || ld >= kMaxColumns; }
-
-// the engine's device made current; its precision
-int enter(nmp_engine* eng, int* precision) {
-  int device = 0;
-  if (nmp_engine_info(eng, &device, precision, nullptr) != NMP_OK) return NMP_E_ARG;
-  int cur = -1;
-  if (hipGetDevice(&cur) != hipSuccess) return NMP_E_DEVICE;
-  if (cur != device && hipSetDevice(device) != hipSuccess) return NMP_E_DEVICE;
-  return NMP_OK;
-}
-
-}  // namespace
-
 }  // namespace nmp
 
 extern "C" {
@@ -163,21 +144,10 @@ int nmp_extremes_update(nmp_engine* eng, int64_t ncol, int64_t ld, int nseries,
   if (!val || !when || (need[NMP_EXT_SRC_DIAG] && !diag) ||
       (need[NMP_EXT_SRC_FORCING] && !forcing) || (need[NMP_EXT_SRC_STATE] && !state))
     return NMP_E_ARG;
-  int precision = 0;
-  if (int rc = nmp::enter(eng, &precision)) return rc;
-  const int64_t grid = (ncol + 255) / 256;
-  hipStream_t st = static_cast<hipStream_t>(stream);
-  if (precision == 4)
-    hipLaunchKernelGGL(nmp::extremes_update_kernel<float>, dim3((unsigned)grid), dim3(256), 0, st,
-                       ncol, ld, nseries, tab, static_cast<const float*>(diag),
-                       static_cast<const float*>(forcing), static_cast<const float*>(state), k,
-                       static_cast<float*>(val), when, ld_ext);
-  else
-    hipLaunchKernelGGL(nmp::extremes_update_kernel<double>, dim3((unsigned)grid), dim3(256), 0, st,
-                       ncol, ld, nseries, tab, static_cast<const double*>(diag),
-                       static_cast<const double*>(forcing), static_cast<const double*>(state), k,
-                       static_cast<double*>(val), when, ld_ext);
-  return hipGetLastError() == hipSuccess ? NMP_OK : NMP_E_DEVICE;
+  if (int rc = nmp::ensure_device(eng->device)) return rc;
+  return nmp::launch_cols(eng->precision, ncol, stream, nmp::extremes_update_kernel<float>,
+                          nmp::extremes_update_kernel<double>, ncol, ld, nseries, tab, diag,
+                          forcing, state, k, val, when, ld_ext);
 }
 
 int nmp_extremes_output(nmp_engine* eng, int64_t ncol, int nseries, const int32_t* stats,
@@ -196,19 +166,10 @@ int nmp_extremes_output(nmp_engine* eng, int64_t ncol, int nseries, const int32_
   }
   if (ncol == 0) return NMP_OK;
   if (!val || !when || !out) return NMP_E_ARG;
-  int precision = 0;
-  if (int rc = nmp::enter(eng, &precision)) return rc;
-  const int64_t grid = (ncol + 255) / 256;
-  hipStream_t st = static_cast<hipStream_t>(stream);
-  if (precision == 4)
-    hipLaunchKernelGGL(nmp::extremes_output_kernel<float>, dim3((unsigned)grid), dim3(256), 0, st,
-                       ncol, nseries, tab, dt, static_cast<const float*>(val), when, ld_ext,
-                       static_cast<float*>(out), ld_out);
-  else
-    hipLaunchKernelGGL(nmp::extremes_output_kernel<double>, dim3((unsigned)grid), dim3(256), 0, st,
-                       ncol, nseries, tab, dt, static_cast<const double*>(val), when, ld_ext,
-                       static_cast<double*>(out), ld_out);
-  return hipGetLastError() == hipSuccess ? NMP_OK : NMP_E_DEVICE;
+  if (int rc = nmp::ensure_device(eng->device)) return rc;
+  return nmp::launch_cols(eng->precision, ncol, stream, nmp::extremes_output_kernel<float>,
+                          nmp::extremes_output_kernel<double>, ncol, nseries, tab, dt, val, when,
+                          ld_ext, out, ld_out);
 }
 
 }  // extern "C"

@@ -8,28 +8,16 @@
 // is one IEEE double operation in the order the header documents (no
 // contraction: the build keeps -ffp-contract=off), each result rounded once to
 // fp32 and then widened to the engine precision, which the numpy restatement
-// in noahmp-1_amd/tinterp.py follows operation for operation.  The COSZ
-// expression is forcing.hip's forcing_ldasin_kernel<T, true>'s, restated.
+// in noahmp-1_amd/tinterp.py follows operation for operation.  COSZ and the
+// 12 stores are col_math.h's cosz_geo and store_forcing.
 #include <hip/hip_runtime.h>
 
 #include <cstdint>
 
-#include "noahmp_engine.h"
+#include "col_math.h"
+#include "engine_impl.h"
 
 namespace nmp {
-
-namespace {
-
-// as engine.hip's: a column's byte offset is formed in 32 bits
-constexpr int64_t kMaxColumns = int64_t(1) << 29;
-
-__device__ __forceinline__ float cosz_geo(const double* __restrict__ g, int64_t ld,
-                                          double sin_decl, double cos_decl, double ha0) {
-  const double ha = (ha0 + g[2 * ld]) - 3.141592653589793;
-  return (float)(g[0] * sin_decl + (g[ld] * cos_decl) * cos(ha));
-}
-
-}  // namespace
 
 __global__ __launch_bounds__(256) void ldasin_cosz_kernel(int64_t ncol, int64_t ld,
                                                           const double* __restrict__ geo,
@@ -37,7 +25,8 @@ __global__ __launch_bounds__(256) void ldasin_cosz_kernel(int64_t ncol, int64_t 
                                                           double ha0, float* __restrict__ block) {
   const int64_t c = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
   if (c >= ncol) return;
-  block[NMP_L_COSZ * ld + c] = cosz_geo(geo + c, ld, sin_decl, cos_decl, ha0);
+  const double* g = geo + c;
+  block[NMP_L_COSZ * ld + c] = cosz_geo(g[0], g[ld], g[2 * ld], sin_decl, cos_decl, ha0);
 }
 
 // ZEN: SWDOWN by the zenith-weighted scheme (the blocks' COSZ rows are read
@@ -66,8 +55,7 @@ __global__ __launch_bounds__(256) void forcing_interp_kernel(
     cz1 = i1[NMP_L_COSZ * ld];
   }
   const double g0 = g[0], g1 = g[ld], g2 = g[2 * ld];
-  const double ha = (ha0 + g2) - 3.141592653589793;
-  const float cosz = (float)(g0 * sin_decl + (g1 * cos_decl) * cos(ha));
+  const float cosz = cosz_geo(g0, g1, g2, sin_decl, cos_decl, ha0);
   float r[NMP_L_COSZ];
 #pragma unroll
   for (int v = 0; v < NMP_L_COSZ; ++v) {
@@ -86,33 +74,7 @@ __global__ __launch_bounds__(256) void forcing_interp_kernel(
       r[v] = (float)((double)a[v] * w0 + (double)b[v] * w1);
     }
   }
-  const float psfc = r[NMP_L_PSFC];
-  T* o = out + c;
-  o[NMP_A_SFCTMP * ld] = (T)r[NMP_L_T2D];
-  o[NMP_A_SFCPRS * ld] = (T)psfc;
-  o[NMP_A_PSFC * ld] = (T)psfc;
-  o[NMP_A_UU * ld] = (T)r[NMP_L_U2D];
-  o[NMP_A_VV * ld] = (T)r[NMP_L_V2D];
-  o[NMP_A_Q2 * ld] = (T)r[NMP_L_Q2D];
-  o[NMP_A_SOLDN * ld] = (T)r[NMP_L_SWDOWN];
-  o[NMP_A_LWDN * ld] = (T)r[NMP_L_LWDOWN];
-  o[NMP_A_PRCP * ld] = (T)r[NMP_L_RAINRATE];
-  o[NMP_A_COSZ * ld] = (T)cosz;
-  o[NMP_A_CO2AIR * ld] = (T)(float)(395.0e-6 * (double)psfc);
-  o[NMP_A_O2AIR * ld] = (T)(float)(0.209 * (double)psfc);
-}
-
-template <class T>
-static void launch_interp_t(int64_t grid, int64_t ncol, int64_t ld, const float* in0,
-                            const float* in1, double w0, double w1, uint32_t hold_mask, bool zen,
-                            double floor, const double* geo, double sd, double cd, double ha0,
-                            T* out, hipStream_t stream) {
-  if (zen)
-    hipLaunchKernelGGL((forcing_interp_kernel<T, true>), dim3((unsigned)grid), dim3(256), 0,
-                       stream, ncol, ld, in0, in1, w0, w1, hold_mask, floor, geo, sd, cd, ha0, out);
-  else
-    hipLaunchKernelGGL((forcing_interp_kernel<T, false>), dim3((unsigned)grid), dim3(256), 0,
-                       stream, ncol, ld, in0, in1, w0, w1, hold_mask, floor, geo, sd, cd, ha0, out);
+  store_forcing(out + c, ld, r, cosz);
 }
 
 }  // namespace nmp
@@ -121,19 +83,12 @@ extern "C" {
 
 int nmp_ldasin_cosz(nmp_engine* eng, int64_t ncol, int64_t ld, const double* geo, double sin_decl,
                     double cos_decl, double ha0, float* ldasin, void* stream) {
-  if (!eng || ncol < 0 || ld < ncol || ld >= nmp::kMaxColumns) return NMP_E_ARG;
+  if (!eng || ncol < 0 || nmp::bad_ld(ld, ncol)) return NMP_E_ARG;
   if (ncol == 0) return NMP_OK;
   if (!geo || !ldasin) return NMP_E_ARG;
-  int device = 0;
-  if (nmp_engine_info(eng, &device, nullptr, nullptr) != NMP_OK) return NMP_E_ARG;
-  int cur = -1;
-  if (hipGetDevice(&cur) != hipSuccess) return NMP_E_DEVICE;
-  if (cur != device && hipSetDevice(device) != hipSuccess) return NMP_E_DEVICE;
-  const int64_t grid = (ncol + 255) / 256;
-  hipLaunchKernelGGL(nmp::ldasin_cosz_kernel, dim3((unsigned)grid), dim3(256), 0,
-                     static_cast<hipStream_t>(stream), ncol, ld, geo, sin_decl, cos_decl, ha0,
-                     ldasin);
-  return hipGetLastError() == hipSuccess ? NMP_OK : NMP_E_DEVICE;
+  if (int rc = nmp::ensure_device(eng->device)) return rc;
+  return nmp::launch_cols(ncol, stream, nmp::ldasin_cosz_kernel, ncol, ld, geo, sin_decl, cos_decl,
+                          ha0, ldasin);
 }
 
 int nmp_forcing_from_ldasin_interp(nmp_engine* eng, int64_t ncol, int64_t ld,
@@ -141,7 +96,7 @@ int nmp_forcing_from_ldasin_interp(nmp_engine* eng, int64_t ncol, int64_t ld,
                                    uint32_t hold_mask, int sw_zenith, double cosz_floor,
                                    const double* geo, double sin_decl, double cos_decl, double ha0,
                                    void* forcing, void* stream) {
-  if (!eng || ncol < 0 || ld < ncol || ld >= nmp::kMaxColumns) return NMP_E_ARG;
+  if (!eng || ncol < 0 || nmp::bad_ld(ld, ncol)) return NMP_E_ARG;
   // the negated forms also refuse NaN
   if (!(w1 >= 0.0 && w1 < 1.0) || (hold_mask >> NMP_L_COSZ) != 0u) return NMP_E_ARG;
   if (sw_zenith && !(cosz_floor > 0.0 && cosz_floor <= 1.0)) return NMP_E_ARG;
@@ -152,22 +107,15 @@ int nmp_forcing_from_ldasin_interp(nmp_engine* eng, int64_t ncol, int64_t ld,
   if (w1 == 0.0)
     return nmp_forcing_from_ldasin_geo(eng, ncol, ld, ldasin0, geo, sin_decl, cos_decl, ha0,
                                        forcing, stream);
-  int device = 0, precision = 0;
-  if (nmp_engine_info(eng, &device, &precision, nullptr) != NMP_OK) return NMP_E_ARG;
-  int cur = -1;
-  if (hipGetDevice(&cur) != hipSuccess) return NMP_E_DEVICE;
-  if (cur != device && hipSetDevice(device) != hipSuccess) return NMP_E_DEVICE;
+  if (int rc = nmp::ensure_device(eng->device)) return rc;
   const double w0 = 1.0 - w1;
-  const bool zen = sw_zenith && !((hold_mask >> NMP_L_SWDOWN) & 1u);
-  const int64_t grid = (ncol + 255) / 256;
-  hipStream_t st = static_cast<hipStream_t>(stream);
-  if (precision == 4)
-    nmp::launch_interp_t(grid, ncol, ld, ldasin0, ldasin1, w0, w1, hold_mask, zen, cosz_floor, geo,
-                         sin_decl, cos_decl, ha0, static_cast<float*>(forcing), st);
-  else
-    nmp::launch_interp_t(grid, ncol, ld, ldasin0, ldasin1, w0, w1, hold_mask, zen, cosz_floor, geo,
-                         sin_decl, cos_decl, ha0, static_cast<double*>(forcing), st);
-  return hipGetLastError() == hipSuccess ? NMP_OK : NMP_E_DEVICE;
+  if (sw_zenith && !((hold_mask >> NMP_L_SWDOWN) & 1u))
+    return nmp::launch_cols(eng->precision, ncol, stream, nmp::forcing_interp_kernel<float, true>,
+                            nmp::forcing_interp_kernel<double, true>, ncol, ld, ldasin0, ldasin1,
+                            w0, w1, hold_mask, cosz_floor, geo, sin_decl, cos_decl, ha0, forcing);
+  return nmp::launch_cols(eng->precision, ncol, stream, nmp::forcing_interp_kernel<float, false>,
+                          nmp::forcing_interp_kernel<double, false>, ncol, ld, ldasin0, ldasin1,
+                          w0, w1, hold_mask, cosz_floor, geo, sin_decl, cos_decl, ha0, forcing);
 }
 
 }  // extern "C"

@@ -18,6 +18,8 @@
 
 #include <cstdint>
 
+#include "engine_impl.h"
+
 namespace nmp {
 
 constexpr int kRebinBuckets = 32;  // keys >= 31 share the last bucket
@@ -51,13 +53,21 @@ __global__ __launch_bounds__(256) void rebin_order_kernel(const uint8_t* __restr
   }
 }
 
-hipError_t launch_rebin(const uint8_t* cost, int32_t* order, int64_t ncol, int tile,
-                        hipStream_t stream) {
+}  // namespace nmp
+
+extern "C" {
+
+int nmp_rebin(nmp_engine* eng, int64_t ncol, const uint8_t* cost, int32_t* order, int32_t tile,
+              void* stream) {
+  if (!eng || ncol < 0 || !cost || !order || ncol > INT32_MAX) return NMP_E_ARG;
+  if (tile < 64 || tile > (1 << 20) || tile % 64 != 0) return NMP_E_ARG;
+  if (ncol == 0) return NMP_OK;
+  if (int rc = nmp::ensure_device(eng->device)) return rc;
+  // one workgroup per tile
   const int64_t grid = (ncol + tile - 1) / tile;
-  if (grid == 0) return hipSuccess;
-  hipLaunchKernelGGL(rebin_order_kernel, dim3((unsigned)grid), dim3(256), 0, stream, cost, order,
-                     ncol, tile);
-  return hipGetLastError();
+  hipLaunchKernelGGL(nmp::rebin_order_kernel, dim3((unsigned)grid), dim3(256), 0,
+                     static_cast<hipStream_t>(stream), cost, order, ncol, tile);
+  return nmp::rc_of(hipGetLastError());
 }
 
-}  // namespace nmp
+}  // extern "C"

@@ -8,17 +8,15 @@
 // numpy).  It does not depend on the launch shape, the stream or the engine
 // precision's width, there are no atomics and no completion flags, and every
 // operation is one IEEE double operation (the build has -ffp-contract=off),
-// so a host reproduces every bit:
+// so a host reproduces every bit.  Its pieces are col_math.h's:
 //
-//   pass 1  one wavefront per chunk of NMP_REGION_CHUNK = 256 plan entries;
-//           lane l adds, from +0.0 and in this order, the rounded products
-//           (double)v * w of entries l, l+64, l+128, l+192 (pad entries,
-//           entry_col < 0, are skipped: not loaded, not multiplied); then the
-//           xor butterfly x = x + shfl_xor(x, s) for s = 32, 16, 8, 4, 2, 1;
-//           lane 0 writes partial[f*nchunk + k].
+//   pass 1  one wavefront per chunk of NMP_REGION_CHUNK plan entries; the
+//           terms are the rounded products (double)v * w (pad entries,
+//           entry_col < 0, are skipped: not loaded, not multiplied); lane 0
+//           writes partial[f*nchunk + k].
 //   pass 2  per (region, field), by one thread or, for plans of long regions,
-//           one wavefront (the same sequence): from +0.0, the region's chunk
-//           partials added in chunk order; sums[f*nreg + r], and, where asked,
+//           one wavefront (the same sequence): the region's chunk partials
+//           added in chunk order; sums[f*nreg + r], and, where asked,
 //           means[f*nreg + r] = sum / wsum[r] (one division; 0/0 = NaN for a
 //           region without chunks).
 //
@@ -27,24 +25,21 @@
 #include <hip/hip_runtime.h>
 
 #include <cstdint>
+#include <mutex>
 
-#include "noahmp_engine.h"
-#include "sflx_kargs.h"
+#include "col_math.h"
+#include "engine_impl.h"
 
 namespace nmp {
 
 namespace {
 
-constexpr int kWave = 64;
-constexpr int kPerLane = NMP_REGION_CHUNK / kWave;  // 4 entries per lane
-constexpr int kWavesPerBlock = 4;
+static_assert(NMP_REGION_CHUNK == kWave * kPerLane, "one wavefront per chunk");
 
 // G fields of one chunk: all of the lane's loads first (G x 4 independent
 // nontemporal loads in flight), then each field's four adds and its butterfly.
 // FULL: the chunk has no pad (every chunk of a region but its last, as a
-// rule), so loads and adds carry no predicate -- the same operations in the
-// same order; with predicates the compiler branches around every load and
-// waits for each (measured 2.3x the time in fp32).
+// rule; col_math.h chunk_full).
 template <class T, int G, bool FULL>
 __device__ __forceinline__ void reduce_fields(const T* __restrict__ fields, int64_t ld, int f0,
                                               const int32_t (&col)[kPerLane],
@@ -69,8 +64,7 @@ __device__ __forceinline__ void reduce_fields(const T* __restrict__ fields, int6
 #pragma unroll
     for (int j = 0; j < kPerLane; ++j)
       if (FULL || col[j] >= 0) x = x + (double)v[g][j] * w[j];
-#pragma unroll
-    for (int s = kWave / 2; s >= 1; s >>= 1) x = x + __shfl_xor(x, s, kWave);
+    x = wave_sum(x);
     if (lane == 0) out[(int64_t)(f0 + g) * nchunk] = x;
   }
 }
@@ -111,8 +105,8 @@ __global__ __launch_bounds__(kWave* kWavesPerBlock) void region_pass1_kernel(
     w[j] = __builtin_nontemporal_load(entry_w + e);
   }
   double* out = partial + k;
-  // wave-uniform: no lane of this chunk holds a pad
-  if (__all(col[0] >= 0 && col[1] >= 0 && col[2] >= 0 && col[3] >= 0))
+  const bool ok[kPerLane] = {col[0] >= 0, col[1] >= 0, col[2] >= 0, col[3] >= 0};
+  if (chunk_full(ok))
     reduce_chunk<T, true>(fields, ld, nfield, col, w, lane, out, nchunk);
   else
     reduce_chunk<T, false>(fields, ld, nfield, col, w, lane, out, nchunk);
@@ -147,10 +141,8 @@ __global__ __launch_bounds__(256) void region_pass2_kernel(
 }
 
 // The same sums for plans of long regions (one basin over a million columns
-// is 4,096 partials): one wavefront per (region, field).  The lanes load 64
-// consecutive partials at once, the next 64 while these are added, and every
-// lane adds them in chunk order from the lanes' registers -- the sequential
-// tree of region_pass2_kernel, bit for bit, without a memory latency per batch.
+// is 4,096 partials): one wavefront per (region, field), the sequential tree
+// of region_pass2_kernel, bit for bit.
 __global__ __launch_bounds__(kWave* kWavesPerBlock) void region_pass2_wave_kernel(
     int nfield, int64_t nchunk, int64_t nreg, const int64_t* __restrict__ region_chunk0,
     const double* __restrict__ wsum, const double* __restrict__ partial,
@@ -162,26 +154,7 @@ __global__ __launch_bounds__(kWave* kWavesPerBlock) void region_pass2_wave_kerne
   int64_t k0 = region_chunk0[r], k1 = region_chunk0[r + 1];
   if (k0 < 0) k0 = 0;
   if (k1 > nchunk) k1 = nchunk;
-  const double* p = partial + f * nchunk;
-  double sum = 0.0;
-  double v = k0 + lane < k1 ? p[k0 + lane] : 0.0;
-  for (int64_t k = k0; k < k1; k += kWave) {
-    const double next = k + kWave + lane < k1 ? p[k + kWave + lane] : 0.0;
-    // lane i's partial to every lane (i is uniform: two v_readlane_b32)
-    const int lo = __double2loint(v), hi = __double2hiint(v);
-    if (k1 - k >= kWave) {
-#pragma unroll
-      for (int i = 0; i < kWave; ++i)
-        sum = sum + __hiloint2double(__builtin_amdgcn_readlane(hi, i),
-                                     __builtin_amdgcn_readlane(lo, i));
-    } else {
-      const int m = (int)(k1 - k);
-      for (int i = 0; i < m; ++i)
-        sum = sum + __hiloint2double(__builtin_amdgcn_readlane(hi, i),
-                                     __builtin_amdgcn_readlane(lo, i));
-    }
-    v = next;
-  }
+  const double sum = wave_ordered_sum(partial + f * nchunk, k0, k1, lane);
   if (lane == 0) {
     sums[f * nreg + r] = sum;
     if (means) means[f * nreg + r] = sum / wsum[r];
@@ -190,38 +163,53 @@ __global__ __launch_bounds__(kWave* kWavesPerBlock) void region_pass2_wave_kerne
 
 // average chunks per region from which pass 2 runs one wave per (region, field)
 constexpr int64_t kPass2WaveMinChunks = 32;
+// most fields one nmp_region_reduce call takes (its launches count
+// nreg x nfield threads in 64 bits and blocks in 32)
+constexpr int kMaxRegionFields = 1024;
 
 }  // namespace
 
-hipError_t launch_region_reduce(int precision, int64_t ncol, int64_t ld, int nfield,
-                                const void* fields, int64_t nchunk, const int32_t* entry_col,
-                                const double* entry_w, int64_t nreg, const int64_t* region_chunk0,
-                                const double* wsum, double* partial, double* sums, double* means,
-                                hipStream_t stream) {
-  if (nchunk <= 0 || nreg <= 0 || nfield <= 0) return hipSuccess;
-  const int64_t grid1 = (nchunk + kWavesPerBlock - 1) / kWavesPerBlock;
-  if (precision == 4)
-    hipLaunchKernelGGL(region_pass1_kernel<float>, dim3((unsigned)grid1),
-                       dim3(kWave * kWavesPerBlock), 0, stream, ncol, ld, nfield,
+}  // namespace nmp
+
+extern "C" {
+
+int nmp_region_reduce(nmp_engine* eng, int64_t ncol, int64_t ld, int nfield, const void* fields,
+                      int64_t nchunk, const int32_t* entry_col, const double* entry_w,
+                      int64_t nreg, const int64_t* region_chunk0, const double* wsum,
+                      double* partial, double* sums, double* means, void* stream) {
+  using namespace nmp;
+  if (!eng || ncol < 0 || bad_ld(ld, ncol) || nfield < 1 || nfield > kMaxRegionFields ||
+      nchunk < 0 || nchunk >= kMaxColumns || nreg < 0 || nreg >= kMaxColumns ||
+      nreg * nfield / 256 >= INT32_MAX)
+    return NMP_E_ARG;
+  if (nchunk == 0 || nreg == 0) return NMP_OK;
+  if (!fields || !entry_col || !entry_w || !region_chunk0 || !wsum || !partial || !sums)
+    return NMP_E_ARG;
+  if (int rc = ensure_device(eng->device)) return rc;
+  // the two passes of one call are enqueued back to back
+  std::lock_guard<std::mutex> lk(eng->host_mu);
+  const hipStream_t st = static_cast<hipStream_t>(stream);
+  const dim3 block(kWave * kWavesPerBlock);
+  const dim3 grid1((unsigned)((nchunk + kWavesPerBlock - 1) / kWavesPerBlock));
+  if (eng->precision == 4)
+    hipLaunchKernelGGL(region_pass1_kernel<float>, grid1, block, 0, st, ncol, ld, nfield,
                        static_cast<const float*>(fields), nchunk, entry_col, entry_w, partial);
   else
-    hipLaunchKernelGGL(region_pass1_kernel<double>, dim3((unsigned)grid1),
-                       dim3(kWave * kWavesPerBlock), 0, stream, ncol, ld, nfield,
+    hipLaunchKernelGGL(region_pass1_kernel<double>, grid1, block, 0, st, ncol, ld, nfield,
                        static_cast<const double*>(fields), nchunk, entry_col, entry_w, partial);
-  hipError_t e = hipGetLastError();
-  if (e != hipSuccess) return e;
+  if (int rc = rc_of(hipGetLastError())) return rc;
   // which of the two pass-2 kernels runs changes the time, never a bit
   if (nchunk >= kPass2WaveMinChunks * nreg) {
     const int64_t grid2 = (nreg * nfield + kWavesPerBlock - 1) / kWavesPerBlock;
-    hipLaunchKernelGGL(region_pass2_wave_kernel, dim3((unsigned)grid2),
-                       dim3(kWave * kWavesPerBlock), 0, stream, nfield, nchunk, nreg,
-                       region_chunk0, wsum, partial, sums, means);
+    hipLaunchKernelGGL(region_pass2_wave_kernel, dim3((unsigned)grid2), block, 0, st, nfield,
+                       nchunk, nreg, region_chunk0, wsum, partial, sums, means);
   } else {
     const int64_t grid2 = (nreg * nfield + 255) / 256;
-    hipLaunchKernelGGL(region_pass2_kernel, dim3((unsigned)grid2), dim3(256), 0, stream, nfield,
+    hipLaunchKernelGGL(region_pass2_kernel, dim3((unsigned)grid2), dim3(256), 0, st, nfield,
                        nchunk, nreg, region_chunk0, wsum, partial, sums, means);
   }
-  return hipGetLastError();
+  return rc_of(hipGetLastError());
 }
 
-}  // namespace nmp
+}  // extern "C"
+

@@ -13,8 +13,7 @@
 
 #include <cstdint>
 
-#include "noahmp_engine.h"
-#include "sflx_kargs.h"
+#include "engine_impl.h"
 
 namespace nmp {
 
@@ -84,17 +83,6 @@ __global__ __launch_bounds__(256) void ldasin_regrid_kernel(int64_t ncol, int64_
   }
 }
 
-hipError_t launch_ldasin_regrid(int64_t ncol, int64_t ld, int64_t npts, const void* grid_be,
-                                const int32_t* corner, const double* weight,
-                                uint32_t nearest_mask, float* block, hipStream_t stream) {
-  const int64_t grid = (ncol + 255) / 256;
-  if (grid == 0) return hipSuccess;
-  hipLaunchKernelGGL(ldasin_regrid_kernel, dim3((unsigned)grid), dim3(256), 0, stream, ncol, ld,
-                     npts, static_cast<const uint32_t*>(grid_be), corner, weight, nearest_mask,
-                     block);
-  return hipGetLastError();
-}
-
 // Elevation (lapse-rate) downscaling of a block in place: temperature by the
 // lapse rate, pressure hypsometrically at the layer's mean temperature,
 // specific humidity at constant relative humidity (Magnus form) and longwave
@@ -129,13 +117,29 @@ __global__ __launch_bounds__(256) void ldasin_downscale_kernel(int64_t ncol, int
   b[NMP_L_LWDOWN * ld] = (float)lw1;
 }
 
-hipError_t launch_ldasin_downscale(int64_t ncol, int64_t ld, const float* dz, double lapse,
-                                   float* block, hipStream_t stream) {
-  const int64_t grid = (ncol + 255) / 256;
-  if (grid == 0) return hipSuccess;
-  hipLaunchKernelGGL(ldasin_downscale_kernel, dim3((unsigned)grid), dim3(256), 0, stream, ncol,
-                     ld, dz, lapse, block);
-  return hipGetLastError();
+}  // namespace nmp
+
+extern "C" {
+
+int nmp_ldasin_regrid(nmp_engine* eng, int64_t ncol, int64_t ld, int64_t npts,
+                      const void* grid_be, const int32_t* corner, const double* weight,
+                      uint32_t nearest_mask, float* ldasin, void* stream) {
+  if (!eng || ncol < 0 || nmp::bad_ld(ld, ncol) || npts < 1 || npts >= nmp::kMaxColumns)
+    return NMP_E_ARG;
+  if (ncol == 0) return NMP_OK;
+  if (!grid_be || !corner || !weight || !ldasin) return NMP_E_ARG;
+  if (int rc = nmp::ensure_device(eng->device)) return rc;
+  return nmp::launch_cols(ncol, stream, nmp::ldasin_regrid_kernel, ncol, ld, npts, grid_be, corner,
+                          weight, nearest_mask, ldasin);
 }
 
-}  // namespace nmp
+int nmp_ldasin_downscale(nmp_engine* eng, int64_t ncol, int64_t ld, const float* dz, double lapse,
+                         float* ldasin, void* stream) {
+  if (!eng || ncol < 0 || nmp::bad_ld(ld, ncol)) return NMP_E_ARG;
+  if (ncol == 0) return NMP_OK;
+  if (!dz || !ldasin) return NMP_E_ARG;
+  if (int rc = nmp::ensure_device(eng->device)) return rc;
+  return nmp::launch_cols(ncol, stream, nmp::ldasin_downscale_kernel, ncol, ld, dz, lapse, ldasin);
+}
+
+}  // extern "C"

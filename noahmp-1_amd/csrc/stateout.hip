@@ -20,9 +20,8 @@
 
 #include <cstdint>
 
-#include "dev_params.h"
-#include "noahmp_engine.h"
-#include "sflx_kargs.h"
+#include "col_math.h"
+#include "engine_impl.h"
 
 namespace nmp {
 
@@ -67,11 +66,13 @@ __global__ __launch_bounds__(256) void state_output_kernel(int64_t ncol, int64_t
     for (int i = 0; i < NMP_NSOIL; ++i) smc[i] = s[(NMP_S_SMC + i) * ld];
   }
   if (groups & kNeedDz) {
+    // ZSNSO's soil rows are C index 2..6; the first, the snow pack's bottom,
+    // is used (and loaded) only under snow
+    T z[NMP_NSOIL + 1];
+    z[0] = isn == 0 ? (T)0 : s[(NMP_S_ZSNSO + 2) * ld];
 #pragma unroll
-    for (int iz = 1; iz <= NMP_NSOIL; ++iz) {
-      const T zb = s[(NMP_S_ZSNSO + iz + 2) * ld];
-      dz[iz - 1] = iz == isn + 1 ? -zb : s[(NMP_S_ZSNSO + iz + 1) * ld] - zb;
-    }
+    for (int i = 1; i <= NMP_NSOIL; ++i) z[i] = s[(NMP_S_ZSNSO + 2 + i) * ld];
+    soil_thickness(z, isn, dz);
   }
 
   if (groups & xbit(NMP_X_SOIL_M)) {
@@ -117,11 +118,9 @@ __global__ __launch_bounds__(256) void state_output_kernel(int64_t ncol, int64_t
   }
   if (groups & xbit(NMP_X_TWS)) {
     T w = (T)0;
-    if (static_i[NMP_I_IST * ld + c] == 1) {
-      w = ((s[NMP_S_CANLIQ * ld] + s[NMP_S_CANICE * ld]) + s[NMP_S_SNEQV * ld]) + s[NMP_S_WA * ld];
-#pragma unroll
-      for (int i = 0; i < NMP_NSOIL; ++i) w = w + (smc[i] * dz[i]) * (T)1000;
-    }
+    if (static_i[NMP_I_IST * ld + c] == 1)
+      w = water_storage(s[NMP_S_CANLIQ * ld], s[NMP_S_CANICE * ld], s[NMP_S_SNEQV * ld],
+                        s[NMP_S_WA * ld], smc, dz);
     o[k * ld_out] = w;
     k += 1;
   }
@@ -203,21 +202,22 @@ __global__ __launch_bounds__(256) void state_output_kernel(int64_t ncol, int64_t
   }
 }
 
-hipError_t launch_state_output(int precision, const DevParams* p, int64_t ncol, int64_t ld,
-                               const void* state, const int32_t* isnow, const int32_t* static_i,
-                               uint32_t groups, double fill, void* out, int64_t ld_out,
-                               hipStream_t stream) {
-  const int64_t grid = (ncol + 255) / 256;
-  if (grid == 0) return hipSuccess;
-  if (precision == 4)
-    hipLaunchKernelGGL(state_output_kernel<float>, dim3((unsigned)grid), dim3(256), 0, stream,
-                       ncol, ld, static_cast<const float*>(state), isnow, static_i, p, groups,
-                       (float)fill, static_cast<float*>(out), ld_out);
-  else
-    hipLaunchKernelGGL(state_output_kernel<double>, dim3((unsigned)grid), dim3(256), 0, stream,
-                       ncol, ld, static_cast<const double*>(state), isnow, static_i, p, groups,
-                       fill, static_cast<double*>(out), ld_out);
-  return hipGetLastError();
+}  // namespace nmp
+
+extern "C" {
+
+int nmp_state_output(nmp_engine* eng, int64_t ncol, int64_t ld, const void* state,
+                     const int32_t* isnow, const int32_t* static_i, uint32_t groups,
+                     double fill, void* out, int64_t ld_out, void* stream) {
+  if (!eng || ncol < 0 || nmp::bad_ld(ld, ncol) || nmp::bad_ld(ld_out, ncol) || groups == 0 ||
+      (groups >> NMP_NXGROUP) != 0)
+    return NMP_E_ARG;
+  if (ncol == 0) return NMP_OK;
+  if (!state || !isnow || !static_i || !out) return NMP_E_ARG;
+  if (int rc = nmp::ensure_device(eng->device)) return rc;
+  return nmp::launch_cols(eng->precision, ncol, stream, nmp::state_output_kernel<float>,
+                          nmp::state_output_kernel<double>, ncol, ld, state, isnow, static_i,
+                          eng->dparams, groups, fill, out, ld_out);
 }
 
-}  // namespace nmp
+}  // extern "C"

@@ -10,16 +10,9 @@
 
 #include <cstdint>
 
-#include "noahmp_engine.h"
+#include "engine_impl.h"
 
 namespace nmp {
-
-namespace {
-
-// as engine.hip's: a column's byte offset is formed in 32 bits
-constexpr int64_t kMaxColumns = int64_t(1) << 29;
-
-}  // namespace
 
 // m0 and m1 are launch-uniform: the two rows' bases are scalar.  No special
 // case: w == 0, NaN, -0 and subnormals go through the formula.
@@ -43,29 +36,18 @@ extern "C" {
 
 int nmp_static_monthly(nmp_engine* eng, int64_t ncol, int64_t ld_tab, const float* table12,
                        int m0, int m1, double w, void* out_row, void* stream) {
-  if (!eng || ncol < 0 || ld_tab < ncol || ld_tab >= nmp::kMaxColumns) return NMP_E_ARG;
+  if (!eng || ncol < 0 || nmp::bad_ld(ld_tab, ncol)) return NMP_E_ARG;
   if (m0 < 0 || m0 > 11 || m1 < 0 || m1 > 11) return NMP_E_ARG;
   // the negated form also refuses NaN
   if (!(w >= 0.0 && w < 1.0)) return NMP_E_ARG;
   if (ncol == 0) return NMP_OK;
   if (!table12 || !out_row) return NMP_E_ARG;
-  int device = 0, precision = 0;
-  if (nmp_engine_info(eng, &device, &precision, nullptr) != NMP_OK) return NMP_E_ARG;
-  int cur = -1;
-  if (hipGetDevice(&cur) != hipSuccess) return NMP_E_DEVICE;
-  if (cur != device && hipSetDevice(device) != hipSuccess) return NMP_E_DEVICE;
+  if (int rc = nmp::ensure_device(eng->device)) return rc;
   const double u = 1.0 - w;
   const float* row0 = table12 + (int64_t)m0 * ld_tab;
   const float* row1 = table12 + (int64_t)m1 * ld_tab;
-  const int64_t grid = (ncol + 255) / 256;
-  hipStream_t st = static_cast<hipStream_t>(stream);
-  if (precision == 4)
-    hipLaunchKernelGGL(nmp::static_monthly_kernel<float>, dim3((unsigned)grid), dim3(256), 0, st,
-                       ncol, row0, row1, u, w, static_cast<float*>(out_row));
-  else
-    hipLaunchKernelGGL(nmp::static_monthly_kernel<double>, dim3((unsigned)grid), dim3(256), 0, st,
-                       ncol, row0, row1, u, w, static_cast<double*>(out_row));
-  return hipGetLastError() == hipSuccess ? NMP_OK : NMP_E_DEVICE;
+  return nmp::launch_cols(eng->precision, ncol, stream, nmp::static_monthly_kernel<float>,
+                          nmp::static_monthly_kernel<double>, ncol, row0, row1, u, w, out_row);
 }
 
 }  // extern "C"

@@ -121,17 +121,42 @@ class Engine:
             pass
 
     # ------------------------------------------------------------------------
+    def _check_block(self, t: torch.Tensor, shape: tuple, dtype, what: str):
+        """A contiguous field-major block (or per-column vector) on the engine's
+        device: the library is handed raw pointers offset by a column index."""
+        assert tuple(t.shape) == shape and t.dtype == dtype, (what, tuple(t.shape), t.dtype)
+        assert t.is_contiguous(), what
+        assert t.device.type == "cuda" and t.device.index == self.device, (what, t.device)
+
+    @staticmethod
+    def _cols_range(n: int, cols) -> tuple[int, int]:
+        lo, hi = (0, n) if cols is None else (int(cols[0]), int(cols[1]))
+        assert 0 <= lo <= hi <= n
+        return lo, hi
+
+    def _call(self, name: str, stream, *args):
+        """The library's entry `name`: the engine's handle, `args`, then
+        `stream` (None: the device's current stream); its return code checked."""
+        s = stream if stream is not None else torch.cuda.current_stream(self.device)
+        _lib.check(getattr(self._lib, name)(self._h, *args, C.c_void_p(s.cuda_stream)), name)
+
     def _check_cols(self, cs: ColumnState, forcing: torch.Tensor):
         n = cs.ncol
-        assert cs.state.shape == (L.NSTATE, n) and cs.state.dtype == self.dtype
-        assert cs.state.is_contiguous() and cs.static_f.is_contiguous()
-        assert cs.static_f.shape == (L.NSTATIC_F, n) and cs.static_f.dtype == self.dtype
-        assert cs.static_i.shape == (L.NSTATIC_I, n) and cs.static_i.dtype == torch.int32
-        assert cs.isnow.dtype == torch.int32 and cs.status.dtype == torch.int32
-        assert forcing.shape[-2:] == (L.NFORCING, n) and forcing.dtype == self.dtype
-        assert forcing.is_contiguous()
-        for t in (cs.state, cs.isnow, cs.static_f, cs.static_i, cs.status, forcing):
-            assert t.device.type == "cuda" and t.device.index == self.device, t.device
+        self._check_block(cs.state, (L.NSTATE, n), self.dtype, "state")
+        self._check_block(cs.isnow, (n,), torch.int32, "isnow")
+        self._check_block(cs.static_f, (L.NSTATIC_F, n), self.dtype, "static_f")
+        self._check_block(cs.static_i, (L.NSTATIC_I, n), torch.int32, "static_i")
+        self._check_block(cs.status, (n,), torch.int32, "status")
+        # (leading axes are allowed, as ever: the pointer is the first slice's)
+        self._check_block(forcing, tuple(forcing.shape[:-2]) + (L.NFORCING, n), self.dtype,
+                          "forcing")
+
+    def _check_words(self, t: torch.Tensor, rows: int, size: int, what: str):
+        """(rows, npts) words of `size` bytes, whatever their dtype: a file's
+        big-endian grids."""
+        npts = int(t.shape[1]) if t.dim() == 2 else -1
+        self._check_block(t, (rows, npts), t.dtype, what)
+        assert t.element_size() == size, (what, t.dtype)
 
     def step(self, cs: ColumnState, forcing: torch.Tensor, zsoil, dt: float, julian: float,
              yearlen: int, diag: torch.Tensor | None = None, diag_level: int = L.DIAG_NONE,
@@ -149,23 +174,24 @@ class Engine:
         vege_flux trip count."""
         self._check_cols(cs, forcing)
         n = cs.ncol
-        lo, hi = (0, n) if cols is None else (int(cols[0]), int(cols[1]))
-        assert 0 <= lo <= hi <= n
+        lo, hi = self._cols_range(n, cols)
         if diag_level != L.DIAG_NONE:
             nd = L.NDIAG_FULL if diag_level == L.DIAG_FULL_LEVEL else L.NDIAG_OUT
-            assert diag is not None and diag.shape == (nd, n) and diag.dtype == self.dtype
+            assert diag is not None
             # raw pointers offset by `lo` with rows exactly n apart: a strided view
             # would be written in the wrong places
-            assert diag.is_contiguous()
-            assert diag.device.type == "cuda" and diag.device.index == self.device, diag.device
+            self._check_block(diag, (nd, n), self.dtype, "diag")
         zs = (C.c_float * 4)(*[float(z) for z in zsoil])
-        s = stream if stream is not None else torch.cuda.current_stream(self.device)
+        args = (hi - lo, n, zs, float(dt), float(julian), int(yearlen), _ptr(cs.state, lo),
+                _ptr(cs.isnow, lo), _ptr(cs.static_f, lo), _ptr(cs.static_i, lo),
+                _ptr(forcing, lo), _ptr(diag, lo), int(diag_level), _ptr(cs.status, lo))
         if order is not None or cost is not None:
-            for t, dt_ in ((order, torch.int32), (cost, torch.uint8)):
-                if t is not None:
-                    assert t.shape == (n,) and t.dtype == dt_ and t.is_contiguous()
-                    assert t.device.type == "cuda" and t.device.index == self.device
+            if order is not None:
+                self._check_block(order, (n,), torch.int32, "order")
+            if cost is not None:
+                self._check_block(cost, (n,), torch.uint8, "cost")
             if order is not None and os.environ.get("NMP_CHECK_ORDER") == "1":
+                s = stream if stream is not None else torch.cuda.current_stream(self.device)
                 # nmp_step_binned trusts order to be a permutation (noahmp_engine.h);
                 # the debug check costs a sort and a host sync per launch
                 with torch.cuda.stream(s):
@@ -174,29 +200,19 @@ class Engine:
                                                             device=order.device)))
                 if not ok:
                     raise ValueError(f"order[{lo}:{hi}] is not a permutation of 0..{hi - lo - 1}")
-            _lib.check(self._lib.nmp_step_binned(
-                self._h, hi - lo, n, zs, float(dt), float(julian), int(yearlen),
-                _ptr(cs.state, lo), _ptr(cs.isnow, lo), _ptr(cs.static_f, lo),
-                _ptr(cs.static_i, lo), _ptr(forcing, lo), _ptr(diag, lo), int(diag_level),
-                _ptr(cs.status, lo), _ptr(order, lo), _ptr(cost, lo),
-                C.c_void_p(s.cuda_stream)), "nmp_step_binned")
+            self._call("nmp_step_binned", stream, *args, _ptr(order, lo), _ptr(cost, lo))
             return
-        _lib.check(self._lib.nmp_step(self._h, hi - lo, n, zs, float(dt), float(julian),
-                                      int(yearlen), _ptr(cs.state, lo), _ptr(cs.isnow, lo),
-                                      _ptr(cs.static_f, lo), _ptr(cs.static_i, lo),
-                                      _ptr(forcing, lo), _ptr(diag, lo), int(diag_level),
-                                      _ptr(cs.status, lo), C.c_void_p(s.cuda_stream)), "nmp_step")
+        self._call("nmp_step", stream, *args)
 
     def rebin(self, cost: torch.Tensor, order: torch.Tensor, tile: int, stream=None,
               cols: tuple[int, int] | None = None):
         """nmp_rebin: order[lo:hi] <- the columns lo..hi-1 sorted by cost within
         tiles of `tile` columns (indices relative to lo)."""
         n = int(cost.shape[0])
-        lo, hi = (0, n) if cols is None else (int(cols[0]), int(cols[1]))
-        assert cost.dtype == torch.uint8 and order.dtype == torch.int32 and order.shape == (n,)
-        s = stream if stream is not None else torch.cuda.current_stream(self.device)
-        _lib.check(self._lib.nmp_rebin(self._h, hi - lo, _ptr(cost, lo), _ptr(order, lo),
-                                       int(tile), C.c_void_p(s.cuda_stream)), "nmp_rebin")
+        lo, hi = self._cols_range(n, cols)
+        self._check_block(cost, (n,), torch.uint8, "cost")
+        self._check_block(order, (n,), torch.int32, "order")
+        self._call("nmp_rebin", stream, hi - lo, _ptr(cost, lo), _ptr(order, lo), int(tile))
 
     def forcing_synth(self, climate: torch.Tensor, julian: float, yearlen: int, seed: int,
                       step: int, out: torch.Tensor, first_col: int = 0, stream=None,
@@ -206,17 +222,12 @@ class Engine:
         cols=(lo, hi) generates only those columns (first_col + lo is their
         global index, so ranges and ranks draw the same numbers as one launch)."""
         n = int(climate.shape[1])
-        lo, hi = (0, n) if cols is None else (int(cols[0]), int(cols[1]))
-        assert climate.shape == (L.NCLIM, n) and climate.dtype == self.dtype
-        assert out.shape == (L.NFORCING, n) and out.dtype == self.dtype
-        assert climate.is_contiguous() and out.is_contiguous()
-        for t in (climate, out):
-            assert t.device.type == "cuda" and t.device.index == self.device
-        s = stream if stream is not None else torch.cuda.current_stream(self.device)
-        _lib.check(self._lib.nmp_forcing_synth(self._h, hi - lo, n, _ptr(climate, lo),
-                                               float(julian), int(yearlen), int(seed) & (2**64 - 1),
-                                               int(step), int(first_col) + lo, _ptr(out, lo),
-                                               C.c_void_p(s.cuda_stream)), "nmp_forcing_synth")
+        lo, hi = self._cols_range(n, cols)
+        self._check_block(climate, (L.NCLIM, n), self.dtype, "climate")
+        self._check_block(out, (L.NFORCING, n), self.dtype, "out")
+        self._call("nmp_forcing_synth", stream, hi - lo, n, _ptr(climate, lo), float(julian),
+                   int(yearlen), int(seed) & (2**64 - 1), int(step), int(first_col) + lo,
+                   _ptr(out, lo))
 
     def forcing_from_ldasin(self, ldasin: torch.Tensor, out: torch.Tensor, stream=None,
                             cols: tuple[int, int] | None = None, geo: torch.Tensor | None = None,
@@ -231,24 +242,17 @@ class Engine:
         and solar = timeman.solar_terms(julian, yearlen) instead of read from
         the block's COSZ row."""
         n = int(ldasin.shape[1])
-        lo, hi = (0, n) if cols is None else (int(cols[0]), int(cols[1]))
-        assert 0 <= lo <= hi <= n
-        assert ldasin.shape == (L.NLDASIN, n) and ldasin.dtype == torch.float32
-        assert out.shape == (L.NFORCING, n) and out.dtype == self.dtype
-        assert ldasin.is_contiguous() and out.is_contiguous()
-        for t in (ldasin, out) + ((geo,) if geo is not None else ()):
-            assert t.device.type == "cuda" and t.device.index == self.device
-        s = stream if stream is not None else torch.cuda.current_stream(self.device)
+        lo, hi = self._cols_range(n, cols)
+        self._check_block(ldasin, (L.NLDASIN, n), torch.float32, "ldasin")
+        self._check_block(out, (L.NFORCING, n), self.dtype, "out")
         if geo is None:
-            _lib.check(self._lib.nmp_forcing_from_ldasin(self._h, hi - lo, n, _ptr(ldasin, lo),
-                                                         _ptr(out, lo), C.c_void_p(s.cuda_stream)),
-                       "nmp_forcing_from_ldasin")
+            self._call("nmp_forcing_from_ldasin", stream, hi - lo, n, _ptr(ldasin, lo),
+                       _ptr(out, lo))
             return
-        assert geo.shape == (3, n) and geo.dtype == torch.float64 and geo.is_contiguous()
+        self._check_block(geo, (3, n), torch.float64, "geo")
         sd, cd, ha0 = (float(v) for v in solar)
-        _lib.check(self._lib.nmp_forcing_from_ldasin_geo(
-            self._h, hi - lo, n, _ptr(ldasin, lo), _ptr(geo, lo), sd, cd, ha0, _ptr(out, lo),
-            C.c_void_p(s.cuda_stream)), "nmp_forcing_from_ldasin_geo")
+        self._call("nmp_forcing_from_ldasin_geo", stream, hi - lo, n, _ptr(ldasin, lo),
+                   _ptr(geo, lo), sd, cd, ha0, _ptr(out, lo))
 
     def ldasin_ingest(self, grid_be: torch.Tensor, point: torch.Tensor, out: torch.Tensor,
                       stream=None):
@@ -257,16 +261,11 @@ class Engine:
         the file's big-endian fp32 grids in layout.LDASIN order; column c takes
         grid point point[c] (int32, (n,)).  The COSZ row is left as it is."""
         n = int(out.shape[1])
-        assert grid_be.dim() == 2 and grid_be.shape[0] == L.NLDASIN - 1
-        assert grid_be.element_size() == 4 and grid_be.is_contiguous()
-        assert point.shape == (n,) and point.dtype == torch.int32 and point.is_contiguous()
-        assert out.shape == (L.NLDASIN, n) and out.dtype == torch.float32 and out.is_contiguous()
-        for t in (grid_be, point, out):
-            assert t.device.type == "cuda" and t.device.index == self.device
-        s = stream if stream is not None else torch.cuda.current_stream(self.device)
-        _lib.check(self._lib.nmp_ldasin_ingest(self._h, n, n, int(grid_be.shape[1]),
-                                               _ptr(grid_be, 0), _ptr(point, 0), _ptr(out, 0),
-                                               C.c_void_p(s.cuda_stream)), "nmp_ldasin_ingest")
+        self._check_words(grid_be, L.NLDASIN - 1, 4, "grid_be")
+        self._check_block(point, (n,), torch.int32, "point")
+        self._check_block(out, (L.NLDASIN, n), torch.float32, "out")
+        self._call("nmp_ldasin_ingest", stream, n, n, int(grid_be.shape[1]), _ptr(grid_be),
+                   _ptr(point), _ptr(out))
 
     def ldasin_regrid(self, grid_be: torch.Tensor, plan, out: torch.Tensor,
                       nearest_mask: int = 0, stream=None):
@@ -278,21 +277,16 @@ class Engine:
         weighted source entries.  Bit v of nearest_mask: variable v takes its
         nearest entry (regrid.nearest_mask).  The COSZ row is left as it is."""
         n = int(out.shape[1])
-        assert grid_be.dim() == 2 and grid_be.shape[0] == L.NLDASIN - 1
-        assert grid_be.element_size() == 4 and grid_be.is_contiguous()
+        self._check_words(grid_be, L.NLDASIN - 1, 4, "grid_be")
         assert plan.dev is not None and plan.ncol == n, "plan.to(device) for this block"
         assert plan.npts == int(grid_be.shape[1]), (plan.npts, tuple(grid_be.shape))
         corner, weight = plan.dev["corner"], plan.dev["weight"]
         self._check_block(corner, (4, n), torch.int32, "corner")
         self._check_block(weight, (4, n), torch.float64, "weight")
         self._check_block(out, (L.NLDASIN, n), torch.float32, "out")
-        assert grid_be.device.type == "cuda" and grid_be.device.index == self.device
         assert 0 <= int(nearest_mask) < (1 << (L.NLDASIN - 1))
-        s = stream if stream is not None else torch.cuda.current_stream(self.device)
-        _lib.check(self._lib.nmp_ldasin_regrid(self._h, n, n, plan.npts, _ptr(grid_be, 0),
-                                               _ptr(corner), _ptr(weight), int(nearest_mask),
-                                               _ptr(out, 0), C.c_void_p(s.cuda_stream)),
-                   "nmp_ldasin_regrid")
+        self._call("nmp_ldasin_regrid", stream, n, n, plan.npts, _ptr(grid_be), _ptr(corner),
+                   _ptr(weight), int(nearest_mask), _ptr(out))
 
     def ldasin_downscale(self, block: torch.Tensor, dz: torch.Tensor, lapse: float, stream=None):
         """nmp_ldasin_downscale: rows T2D, Q2D, PSFC and LWDOWN of the
@@ -302,10 +296,7 @@ class Engine:
         n = int(block.shape[1])
         self._check_block(block, (L.NLDASIN, n), torch.float32, "block")
         self._check_block(dz, (n,), torch.float32, "dz")
-        s = stream if stream is not None else torch.cuda.current_stream(self.device)
-        _lib.check(self._lib.nmp_ldasin_downscale(self._h, n, n, _ptr(dz, 0), float(lapse),
-                                                  _ptr(block, 0), C.c_void_p(s.cuda_stream)),
-                   "nmp_ldasin_downscale")
+        self._call("nmp_ldasin_downscale", stream, n, n, _ptr(dz), float(lapse), _ptr(block))
 
     def ldasin_cosz(self, block: torch.Tensor, geo: torch.Tensor,
                     solar: tuple[float, float, float], stream=None,
@@ -319,10 +310,8 @@ class Engine:
         self._check_block(block, (L.NLDASIN, n), torch.float32, "block")
         self._check_block(geo, (3, n), torch.float64, "geo")
         sd, cd, ha0 = (float(v) for v in solar)
-        s = stream if stream is not None else torch.cuda.current_stream(self.device)
-        _lib.check(self._lib.nmp_ldasin_cosz(self._h, hi - lo, n, _ptr(geo, lo), sd, cd, ha0,
-                                             _ptr(block, lo), C.c_void_p(s.cuda_stream)),
-                   "nmp_ldasin_cosz")
+        self._call("nmp_ldasin_cosz", stream, hi - lo, n, _ptr(geo, lo), sd, cd, ha0,
+                   _ptr(block, lo))
 
     def forcing_from_ldasin_interp(self, ldasin0: torch.Tensor, ldasin1: torch.Tensor | None,
                                    w1: float, out: torch.Tensor, geo: torch.Tensor,
@@ -345,11 +334,9 @@ class Engine:
         self._check_block(out, (L.NFORCING, n), self.dtype, "out")
         self._check_block(geo, (3, n), torch.float64, "geo")
         sd, cd, ha0 = (float(v) for v in solar)
-        s = stream if stream is not None else torch.cuda.current_stream(self.device)
-        _lib.check(self._lib.nmp_forcing_from_ldasin_interp(
-            self._h, hi - lo, n, _ptr(ldasin0, lo), _ptr(ldasin1, lo), float(w1), int(hold_mask),
-            int(bool(sw_zenith)), float(cosz_floor), _ptr(geo, lo), sd, cd, ha0, _ptr(out, lo),
-            C.c_void_p(s.cuda_stream)), "nmp_forcing_from_ldasin_interp")
+        self._call("nmp_forcing_from_ldasin_interp", stream, hi - lo, n, _ptr(ldasin0, lo),
+                   _ptr(ldasin1, lo), float(w1), int(hold_mask), int(bool(sw_zenith)),
+                   float(cosz_floor), _ptr(geo, lo), sd, cd, ha0, _ptr(out, lo))
 
     def ldasout_grid(self, diag: torch.Tensor, point: torch.Tensor, out: torch.Tensor,
                      fill: float, stream=None):
@@ -358,31 +345,13 @@ class Engine:
         file's big-endian grids, `fill` off the columns' points (point: int32
         (n,))."""
         nf, n = int(diag.shape[0]), int(diag.shape[1])
-        assert diag.dtype == self.dtype and diag.is_contiguous()
-        assert point.shape == (n,) and point.dtype == torch.int32 and point.is_contiguous()
-        assert out.dim() == 2 and out.shape[0] == nf and out.is_contiguous()
-        assert out.element_size() == self.precision
-        for t in (diag, point, out):
-            assert t.device.type == "cuda" and t.device.index == self.device
-        s = stream if stream is not None else torch.cuda.current_stream(self.device)
-        _lib.check(self._lib.nmp_ldasout_grid(self._h, n, n, int(out.shape[1]), nf, _ptr(diag, 0),
-                                              _ptr(point, 0), float(fill), _ptr(out, 0),
-                                              C.c_void_p(s.cuda_stream)), "nmp_ldasout_grid")
+        self._check_block(diag, (nf, n), self.dtype, "diag")
+        self._check_block(point, (n,), torch.int32, "point")
+        self._check_words(out, nf, self.precision, "out")
+        self._call("nmp_ldasout_grid", stream, n, n, int(out.shape[1]), nf, _ptr(diag),
+                   _ptr(point), float(fill), _ptr(out))
 
     # ---- accumulated output (nmp_accumulate / nmp_water_storage / nmp_accum_finish)
-    def _check_block(self, t: torch.Tensor, shape: tuple, dtype, what: str):
-        """A contiguous field-major block (or per-column vector) on the engine's
-        device: the library is handed raw pointers offset by a column index."""
-        assert tuple(t.shape) == shape and t.dtype == dtype, (what, tuple(t.shape), t.dtype)
-        assert t.is_contiguous(), what
-        assert t.device.type == "cuda" and t.device.index == self.device, (what, t.device)
-
-    @staticmethod
-    def _cols_range(n: int, cols) -> tuple[int, int]:
-        lo, hi = (0, n) if cols is None else (int(cols[0]), int(cols[1]))
-        assert 0 <= lo <= hi <= n
-        return lo, hi
-
     def accumulate(self, diag: torch.Tensor, forcing: torch.Tensor, acc: torch.Tensor, dt: float,
                    stream=None, cols: tuple[int, int] | None = None):
         """nmp_accumulate: acc[f] += diag[f] * dt for the 16 output fluxes a
@@ -395,10 +364,8 @@ class Engine:
         self._check_block(diag, (L.NDIAG_OUT, n), self.dtype, "diag")
         self._check_block(forcing, (L.NFORCING, n), self.dtype, "forcing")
         self._check_block(acc, (L.NACC, n), torch.float64, "acc")
-        s = stream if stream is not None else torch.cuda.current_stream(self.device)
-        _lib.check(self._lib.nmp_accumulate(self._h, hi - lo, n, float(dt), _ptr(diag, lo),
-                                            _ptr(forcing, lo), _ptr(acc, lo),
-                                            C.c_void_p(s.cuda_stream)), "nmp_accumulate")
+        self._call("nmp_accumulate", stream, hi - lo, n, float(dt), _ptr(diag, lo),
+                   _ptr(forcing, lo), _ptr(acc, lo))
 
     def water_storage(self, cs: ColumnState, storage: torch.Tensor, stream=None,
                       cols: tuple[int, int] | None = None):
@@ -411,11 +378,8 @@ class Engine:
         self._check_block(cs.isnow, (n,), torch.int32, "isnow")
         self._check_block(cs.static_i, (L.NSTATIC_I, n), torch.int32, "static_i")
         self._check_block(storage, (n,), self.dtype, "storage")
-        s = stream if stream is not None else torch.cuda.current_stream(self.device)
-        _lib.check(self._lib.nmp_water_storage(self._h, hi - lo, n, _ptr(cs.state, lo),
-                                               _ptr(cs.isnow, lo), _ptr(cs.static_i, lo),
-                                               _ptr(storage, lo), C.c_void_p(s.cuda_stream)),
-                   "nmp_water_storage")
+        self._call("nmp_water_storage", stream, hi - lo, n, _ptr(cs.state, lo), _ptr(cs.isnow, lo),
+                   _ptr(cs.static_i, lo), _ptr(storage, lo))
 
     def accum_finish(self, acc: torch.Tensor, stor_end: torch.Tensor, stor_beg: torch.Tensor,
                      out: torch.Tensor, span_s: float, stream=None,
@@ -432,11 +396,8 @@ class Engine:
         self._check_block(stor_beg, (n,), self.dtype, "stor_beg")
         self._check_block(out, (L.NBUDGET, n), self.dtype, "out")
         assert stor_end.data_ptr() != stor_beg.data_ptr() or n == 0
-        s = stream if stream is not None else torch.cuda.current_stream(self.device)
-        _lib.check(self._lib.nmp_accum_finish(self._h, hi - lo, n, float(span_s), _ptr(acc, lo),
-                                              _ptr(stor_end, lo), _ptr(stor_beg, lo),
-                                              _ptr(out, lo), C.c_void_p(s.cuda_stream)),
-                   "nmp_accum_finish")
+        self._call("nmp_accum_finish", stream, hi - lo, n, float(span_s), _ptr(acc, lo),
+                   _ptr(stor_end, lo), _ptr(stor_beg, lo), _ptr(out, lo))
 
     # ---- state output (nmp_state_output) ---------------------------------------
     def state_output(self, cs: ColumnState, groups: int, out_rows: torch.Tensor, fill: float,
@@ -455,11 +416,8 @@ class Engine:
         self._check_block(cs.isnow, (n,), torch.int32, "isnow")
         self._check_block(cs.static_i, (L.NSTATIC_I, n), torch.int32, "static_i")
         self._check_block(out_rows, (nrow, n), self.dtype, "out_rows")
-        s = stream if stream is not None else torch.cuda.current_stream(self.device)
-        _lib.check(self._lib.nmp_state_output(self._h, hi - lo, n, _ptr(cs.state, lo),
-                                              _ptr(cs.isnow, lo), _ptr(cs.static_i, lo),
-                                              int(groups), float(fill), _ptr(out_rows, lo), n,
-                                              C.c_void_p(s.cuda_stream)), "nmp_state_output")
+        self._call("nmp_state_output", stream, hi - lo, n, _ptr(cs.state, lo), _ptr(cs.isnow, lo),
+                   _ptr(cs.static_i, lo), int(groups), float(fill), _ptr(out_rows, lo), n)
 
     # ---- spin-up drift (nmp_state_drift / nmp_drift_reduce) --------------------
     def state_drift(self, cs: ColumnState, snap: torch.Tensor, drift: torch.Tensor | None = None,
@@ -478,12 +436,8 @@ class Engine:
         self._check_block(snap, (L.NTRACKED, n), self.dtype, "snap")
         if drift is not None:
             self._check_block(drift, (L.NDRIFT, n), self.dtype, "drift")
-        s = stream if stream is not None else torch.cuda.current_stream(self.device)
-        _lib.check(self._lib.nmp_state_drift(self._h, hi - lo, n, _ptr(cs.state, lo),
-                                             _ptr(cs.isnow, lo), _ptr(cs.static_i, lo),
-                                             _ptr(snap, lo), n,
-                                             _ptr(drift, lo) if drift is not None else None, n,
-                                             C.c_void_p(s.cuda_stream)), "nmp_state_drift")
+        self._call("nmp_state_drift", stream, hi - lo, n, _ptr(cs.state, lo), _ptr(cs.isnow, lo),
+                   _ptr(cs.static_i, lo), _ptr(snap, lo), n, _ptr(drift, lo), n)
 
     def drift_reduce(self, drift: torch.Tensor, tol, weight: torch.Tensor | None = None,
                      stream=None):
@@ -553,10 +507,8 @@ class Engine:
         lo, hi = self._cols_range(n, cols)
         self._check_block(table, (12, n), torch.float32, "table")
         self._check_block(out_row, (n,), self.dtype, "out_row")
-        s = stream if stream is not None else torch.cuda.current_stream(self.device)
-        _lib.check(self._lib.nmp_static_monthly(self._h, hi - lo, n, _ptr(table, lo), int(m0),
-                                                int(m1), float(w), _ptr(out_row, lo),
-                                                C.c_void_p(s.cuda_stream)), "nmp_static_monthly")
+        self._call("nmp_static_monthly", stream, hi - lo, n, _ptr(table, lo), int(m0), int(m1),
+                   float(w), _ptr(out_row, lo))
 
     # ---- interval extremes (nmp_extremes_update / nmp_extremes_output) -----------
     def extremes_update(self, kind_rows, k: int, val: torch.Tensor, when: torch.Tensor,
@@ -580,11 +532,9 @@ class Engine:
                               (state, L.NSTATE, "state")):
             if t is not None:
                 self._check_block(t, (rows, n), self.dtype, what)
-        s = stream if stream is not None else torch.cuda.current_stream(self.device)
-        _lib.check(self._lib.nmp_extremes_update(
-            self._h, hi - lo, n, ns, kr.ctypes.data_as(C.POINTER(C.c_int32)), _ptr(diag, lo),
-            _ptr(forcing, lo), _ptr(state, lo), int(k), _ptr(val, lo), _ptr(when, lo), n,
-            C.c_void_p(s.cuda_stream)), "nmp_extremes_update")
+        self._call("nmp_extremes_update", stream, hi - lo, n, ns,
+                   kr.ctypes.data_as(C.POINTER(C.c_int32)), _ptr(diag, lo), _ptr(forcing, lo),
+                   _ptr(state, lo), int(k), _ptr(val, lo), _ptr(when, lo), n)
 
     def extremes_output(self, stats, dt: float, val: torch.Tensor, when: torch.Tensor,
                         out_rows: torch.Tensor, stream=None,
@@ -604,11 +554,9 @@ class Engine:
         if all(0 < int(x) < 16 for x in m):   # (the library refuses any other mask)
             nrow = sum(bin(int(x)).count("1") for x in m)
             self._check_block(out_rows, (nrow, n), self.dtype, "out_rows")
-        s = stream if stream is not None else torch.cuda.current_stream(self.device)
-        _lib.check(self._lib.nmp_extremes_output(
-            self._h, hi - lo, ns, m.ctypes.data_as(C.POINTER(C.c_int32)), float(dt),
-            _ptr(val, lo), _ptr(when, lo), n, _ptr(out_rows, lo), n,
-            C.c_void_p(s.cuda_stream)), "nmp_extremes_output")
+        self._call("nmp_extremes_output", stream, hi - lo, ns,
+                   m.ctypes.data_as(C.POINTER(C.c_int32)), float(dt), _ptr(val, lo), _ptr(when, lo),
+                   n, _ptr(out_rows, lo), n)
 
     # ---- region-aggregated output (nmp_region_reduce) ---------------------------
     def region_reduce(self, fields: torch.Tensor, plan, sums: torch.Tensor,
@@ -631,11 +579,9 @@ class Engine:
         self._check_block(d["entry_w"], (plan.nchunk * L.REGION_CHUNK,), torch.float64, "entry_w")
         self._check_block(d["region_chunk0"], (plan.nreg + 1,), torch.int64, "region_chunk0")
         self._check_block(d["wsum"], (plan.nreg,), torch.float64, "wsum")
-        s = stream if stream is not None else torch.cuda.current_stream(self.device)
-        _lib.check(self._lib.nmp_region_reduce(
-            self._h, n, n, nf, _ptr(fields), plan.nchunk, _ptr(d["entry_col"]), _ptr(d["entry_w"]),
-            plan.nreg, _ptr(d["region_chunk0"]), _ptr(d["wsum"]), _ptr(plan.partial(nf)),
-            _ptr(sums), _ptr(means), C.c_void_p(s.cuda_stream)), "nmp_region_reduce")
+        self._call("nmp_region_reduce", stream, n, n, nf, _ptr(fields), plan.nchunk,
+                   _ptr(d["entry_col"]), _ptr(d["entry_w"]), plan.nreg, _ptr(d["region_chunk0"]),
+                   _ptr(d["wsum"]), _ptr(plan.partial(nf)), _ptr(sums), _ptr(means))
 
     # ---- the reference's other public routines (nmp_frh2o / nmp_calhum) ------
     def frh2o(self, sltyp, tkelv, smc, sh2o, status=None, stream=None):
@@ -669,10 +615,8 @@ class Engine:
             assert status.dtype == torch.int32 and status.is_contiguous() and status.shape == (n,)
             assert status.device.type == "cuda" and status.device.index == self.device
         out = torch.empty(n, dtype=self.dtype, device=tkelv.device)
-        s = stream if stream is not None else torch.cuda.current_stream(self.device)
-        _lib.check(self._lib.nmp_frh2o(self._h, n, _ptr(sltyp), _ptr(tkelv), _ptr(smc), _ptr(sh2o),
-                                       _ptr(out), _ptr(status), C.c_void_p(s.cuda_stream)),
-                   "nmp_frh2o")
+        self._call("nmp_frh2o", stream, n, _ptr(sltyp), _ptr(tkelv), _ptr(smc), _ptr(sh2o),
+                   _ptr(out), _ptr(status))
         return out
 
     def calhum(self, sfctmp, sfcprs, stream=None):
@@ -693,9 +637,7 @@ class Engine:
             assert x.device.type == "cuda" and x.device.index == self.device
         q = torch.empty(n, dtype=self.dtype, device=sfctmp.device)
         d = torch.empty_like(q)
-        s = stream if stream is not None else torch.cuda.current_stream(self.device)
-        _lib.check(self._lib.nmp_calhum(self._h, n, _ptr(sfctmp), _ptr(sfcprs), _ptr(q), _ptr(d),
-                                        C.c_void_p(s.cuda_stream)), "nmp_calhum")
+        self._call("nmp_calhum", stream, n, _ptr(sfctmp), _ptr(sfcprs), _ptr(q), _ptr(d))
         return q, d
 
     def sflx_columns(self, rec: np.ndarray) -> np.ndarray:
@@ -719,29 +661,20 @@ class Engine:
         assert forcings.dim() == 3
         self._check_cols(cs, forcings[0])
         zs = (C.c_float * 4)(*[float(z) for z in zsoil])
-        s = stream if stream is not None else torch.cuda.current_stream(self.device)
         if diag_level != L.DIAG_NONE:
             nd = L.NDIAG_FULL if diag_level == L.DIAG_FULL_LEVEL else L.NDIAG_OUT
-            assert diag is not None and diag.dtype == self.dtype and diag.is_contiguous()
-            assert diag.shape[-2:] == (nd, n) and diag.dim() == (2 if out_every is None else 3)
-            assert diag.device.type == "cuda" and diag.device.index == self.device
+            assert diag is not None and diag.dim() == (2 if out_every is None else 3)
+            self._check_block(diag, tuple(diag.shape[:-2]) + (nd, n), self.dtype, "diag")
+        args = (n, n, zs, float(dt), float(julian0), int(yearlen), int(nsteps), _ptr(cs.state),
+                _ptr(cs.isnow), _ptr(cs.static_f), _ptr(cs.static_i), _ptr(forcings),
+                L.NFORCING * n, forcings.shape[0], _ptr(diag), int(diag_level))
         if out_every is None:
-            _lib.check(self._lib.nmp_run(self._h, n, n, zs, float(dt), float(julian0), int(yearlen),
-                                         int(nsteps), _ptr(cs.state), _ptr(cs.isnow),
-                                         _ptr(cs.static_f), _ptr(cs.static_i), _ptr(forcings),
-                                         L.NFORCING * n, forcings.shape[0], _ptr(diag),
-                                         int(diag_level), _ptr(cs.status),
-                                         C.c_void_p(s.cuda_stream)), "nmp_run")
+            self._call("nmp_run", stream, *args, _ptr(cs.status))
             return
         slots = diag.shape[0] if diag is not None else 1
         dstride = diag[0].numel() if diag is not None else 0
-        _lib.check(self._lib.nmp_run_out(self._h, n, n, zs, float(dt), float(julian0),
-                                         int(yearlen), int(nsteps), _ptr(cs.state),
-                                         _ptr(cs.isnow), _ptr(cs.static_f), _ptr(cs.static_i),
-                                         _ptr(forcings), L.NFORCING * n, forcings.shape[0],
-                                         _ptr(diag), int(diag_level), int(out_every), int(slots),
-                                         int(dstride), _ptr(cs.status),
-                                         C.c_void_p(s.cuda_stream)), "nmp_run_out")
+        self._call("nmp_run_out", stream, *args, int(out_every), int(slots), int(dstride),
+                   _ptr(cs.status))
 
 
 class StreamShards:

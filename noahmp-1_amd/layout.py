@@ -216,5 +216,26 @@ def si(name):
     return STATE_OFF[name][0]
 
 
+def soil_thickness_host(z, isnow):
+    """The four soil layers' thickness (csrc/col_math.h soil_thickness) from
+    z = ZSNSO's five soil rows (C index 2..6, arrays over the columns) and
+    isnow: layer iz = 1..4 is z[iz - 1] - z[iz] thick, -z[iz] where it is the
+    column's top layer (iz == isnow + 1)."""
+    import numpy as np
+    return [np.where(isnow + 1 == iz, -z[iz], z[iz - 1] - z[iz]) for iz in range(1, NSOIL + 1)]
+
+
+def water_storage_host(canliq, canice, sneqv, wa, smc, dz):
+    """The column's water storage (csrc/col_math.h water_storage; the
+    reference's BEG_WB / END_WB) in the arrays' own precision and the
+    reference's operation order, from the four scalars' rows and the four
+    layers' smc and thickness.  Not yet 0 where IST != 1: the caller's test."""
+    T = smc[0].dtype.type
+    w = ((canliq + canice) + sneqv) + wa
+    for i in range(NSOIL):
+        w = w + (smc[i] * dz[i]) * T(1000)
+    return w
+
+
 def options_tuple(opts: dict) -> tuple:
     return tuple(int(opts[k]) for k in OPTION_NAMES)

@@ -99,11 +99,9 @@ def tracked_host(state, isnow, static_i, dtype=None) -> np.ndarray:
             out[L.TRACKED["STC"] + i] = one("STC", L.NSNOW + i)
         for name in ("SNEQV", "WA", "ZWT"):
             out[L.TRACKED[name]] = one(name)
-        w = ((one("CANLIQ") + one("CANICE")) + one("SNEQV")) + one("WA")
-        for iz in range(1, L.NSOIL + 1):              # soil layer iz = C index iz + 2 of ZSNSO
-            zb = one("ZSNSO", iz + 2)
-            dz = np.where(isn + 1 == iz, -zb, one("ZSNSO", iz + 1) - zb)
-            w = w + (one("SMC", iz - 1) * dz) * T(1000)
+        dz = L.soil_thickness_host([one("ZSNSO", 2 + i) for i in range(L.NSOIL + 1)], isn)
+        w = L.water_storage_host(one("CANLIQ"), one("CANICE"), one("SNEQV"), one("WA"),
+                                 [one("SMC", i) for i in range(L.NSOIL)], dz)
         ist = np.asarray(static_i)[L.STATIC_I.index("IST")]
         out[L.TRACKED["TWS"]] = np.where(ist == 1, w, T(0))
         p = [one(n) for n in L.CARBON_POOLS]

@@ -166,10 +166,7 @@ def state_output_host(state, isnow, static_i, params, groups, fill, dtype=None):
     out = []
     with np.errstate(all="ignore"):
         smc = [one("SMC", i) for i in range(4)]
-        dz = []
-        for iz in range(1, 5):                       # soil layer iz = C index iz + 2 of ZSNSO
-            zb = one("ZSNSO", iz + 2)
-            dz.append(np.where(isn + 1 == iz, -zb, one("ZSNSO", iz + 1) - zb))
+        dz = L.soil_thickness_host([one("ZSNSO", 2 + i) for i in range(5)], isn)
         active = [k >= isn + 3 for k in range(3)]
         if sel("SOIL_M"):
             out += smc
@@ -190,9 +187,7 @@ def state_output_host(state, isnow, static_i, params, groups, fill, dtype=None):
                 x = np.where(active[k], x + one("SNLIQ", k), x)
             out.append(x)
         if sel("TWS"):
-            w = ((one("CANLIQ") + one("CANICE")) + one("SNEQV")) + one("WA")
-            for i in range(4):
-                w = w + (smc[i] * dz[i]) * T(1000)
+            w = L.water_storage_host(one("CANLIQ"), one("CANICE"), one("SNEQV"), one("WA"), smc, dz)
             out.append(np.where(static_i[L.STATIC_I.index("IST")] == 1, w, T(0)))
         if sel("SOILSAT"):
             typ = np.asarray(static_i[L.STATIC_I.index("SOILTYP")], np.int64)

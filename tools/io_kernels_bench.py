@@ -37,6 +37,8 @@ achieved HBM bandwidth against their algorithmic bytes, at 1,048,576 columns.
                            the SHDFAC row (4 B fp32, 8 B fp64)
   accumulate               reads 16 flux rows and PRCP, reads and writes the 17
                            double accumulators (340 B fp32, 408 B fp64)
+  water_storage            reads IST and, of a soil column, ISNOW and 13 state
+                           rows (counted for every column), writes one value
   extremes_update          a step past the interval's first that sets no new
                            extreme: per series reads the value and the running
                            maximum and minimum (12 B fp32, 24 B fp64), writes
@@ -223,6 +225,9 @@ def main():
         frc = torch.as_tensor(rng.normal(size=(L.NFORCING, n)), device=dev).to(dt)
         cases.append(("accumulate", None, lambda: eng.accumulate(diag, frc, acc, 900.0),
                       n * (17 * prec + 2 * 17 * 8)))
+        stor = torch.empty(n, dtype=dt, device=dev)
+        cases.append(("water_storage", None, lambda: eng.water_storage(so_cs[prec], stor),
+                      n * (13 * prec + 8 + prec)))
         for spec in ("T2M,PRCP,TG,SNEQV",
                      "FSH,TRAD,T2M,RUNSRF,RUNSUB,ALBEDO,PRCP,SFCTMP,TG,TV,SNEQV,SNOWH,SMC1,"
                      "SH2O1,STC1,ZWT"):
