@@ -46,8 +46,9 @@ diagnostics are gathered to rank 0 (shard.DiagGather, dst=0, ragged shards
 allowed), which writes them for the whole grid.
 
 How the forcing reaches the GPU is feeds.py's (one feed per forcing path, chosen
-by `feeds.feed_kind`); the output files and the accumulators are output.py's
-(`OutputWriter`, `Accumulation`).  `OfflineDriver` is the loop around them.
+by `feeds.feed_kind`); the output rows' producers, the `OutputBlock` that lays
+them out and plans each step for them, and the files' `OutputWriter` are
+output.py's.  `OfflineDriver` is the loop around them.
 
 `phase_s` accumulates the host time of the loop's parts (file headers,
 forcing, launch enqueue, output hand-off, the whole iteration), for the
@@ -70,7 +71,7 @@ from .engine import ColumnState, Engine, StreamShards
 from .feeds import (DeviceSyntheticForcing, ForcingUpload, HostFeed,  # noqa: F401  (re-exported)
                     SyntheticForcing, feed_kind, make_feed)
 from .order import coherent_order
-from .output import Accumulation, Extremes, OutputWriter
+from .output import OutputBlock, OutputWriter, chain
 from .params import Params
 from .regions import area_weights, plan_from_args
 
@@ -225,8 +226,8 @@ class OfflineDriver:
         seconds from the interval's start to the end of the step that set the
         extreme) after the fluxes and the budget rows and before the state
         rows.  With a series of the output fluxes every step writes its fluxes
-        (DIAG_OUT_LEVEL; into the scratch block accumulation uses when both are
-        on); without one the steps between output steps stay at DIAG_NONE.
+        (DIAG_OUT_LEVEL; into the one scratch block that accumulation reads
+        too); without one the steps between output steps stay at DIAG_NONE.
         REGIONS files carry the rows; restarts carry the interval so far
         (save_restart).  Refused in a run that writes no output.  None (the
         default): every code path and output byte is as without it."""
@@ -288,27 +289,13 @@ class OfflineDriver:
         self.spinup_history, self.spinup_stop = [], None
         self._spin = None
         self.accumulate = bool(accumulate)
-        self.out_names = L.DIAG_OUT_ACC if self.accumulate else L.DIAG_OUT
-        self.nflux, region_rows = len(self.out_names), None
-        # the interval's extremes: their rows follow the fluxes (and the budget rows)
-        self.extremes, self.next = None, 0
-        if ext_series is not None:
-            self.extremes = Extremes(self.engine, self.cs, ext_series, self.dt,
-                                     scratch=not self.accumulate)
-            self.out_names = list(self.out_names) + self.extremes.names
-            self.next = len(self.extremes.names)
-        if self.state_mask:
-            # the block's rows: the fluxes, the extremes rows, then the selected
-            # state rows, the groups that can hold the fill value last; the
-            # regions stop before them
-            self.out_names = list(self.out_names) + stateout.row_names(self.state_mask)
-            region_rows = self.nflux + self.next + stateout.nofill_rows(self.state_mask)
+        # the output rows: their producers, layout and per-step plan (output.OutputBlock)
+        block = self.block = OutputBlock(self.engine, self.cs, self.dt, self.accumulate,
+                                         ext_series, self.state_mask)
+        self.out_names, self.diag = block.names, block.diag
+        self.accum, self.extremes = block.accum, block.extremes
         nout = len(self.out_names)
-        self.diag = torch.zeros((nout, self.cs.ncol), dtype=self.dtype, device=self.dev)
-        self.accum = None
-        if self.accumulate:
-            self.accum = Accumulation(self.engine, self.cs, self.dt)
-        if (self.accumulate or self.state_mask or self.extremes is not None) and grid is not None:
+        if nout > L.NDIAG_OUT and grid is not None:
             # a grid whose 35 fields or state rows do not pass the classic
             # format's offsets fails here, not on a writer thread after the
             # first interval
@@ -340,9 +327,9 @@ class OfflineDriver:
             lat = cols.static_f[L.STATIC_F.index("LAT")] if total == cols.n else None
             self.region_plan = plan_from_args(regions, region_weights, total, lat).to(self.dev)
         # the output staging buffers up front, out of the time loop (OutputWriter)
-        self.output = OutputWriter(self.engine, cfg, grid, self.out_names, total, self.dtype,
-                                   self.dev, write and cfg.output_interval is not None and rank0,
-                                   self.region_plan, self.write_grids, region_rows=region_rows)
+        self.output = OutputWriter(self.engine, cfg, grid, block, total, self.dtype, self.dev,
+                                   write and cfg.output_interval is not None and rank0,
+                                   self.region_plan, self.write_grids)
         self.written, self.regions_written = self.output.written, self.output.regions_written
         self.n_out = 0
 
@@ -409,12 +396,8 @@ class OfflineDriver:
         drv.t, drv.step_index = t0, step
         drv._start = (t0, step)
         drv.perm, drv.cols_index, drv.output.perm = perm, idx, perm
-        if drv.accumulate:
-            a = ncio.read_accum(init or cfg.initfile, grid)
-            if a is not None:  # a restart written part way through an interval
-                drv.accum.restore(a, idx)
-        if drv.extremes is not None:
-            drv.extremes.restore(ncio.read_extremes(init or cfg.initfile, grid), idx)
+        for p in drv.block.carried:  # an initialization file written part way through an interval
+            p.restore(p.nc[1](init or cfg.initfile, grid), idx)
         return drv
 
     @property
@@ -433,30 +416,21 @@ class OfflineDriver:
 
     # ---- restart -----------------------------------------------------------------
     def save_restart(self, path: str):
-        """With accumulation on, the interval so far travels with the state:
-        the accumulators, the interval's beginning storage and the number of
-        steps accumulated (npz: arrays acc, stor_beg, acc_steps; netCDF:
-        ncio.write_state's accum).  With extremes on, so do the running
-        extremes, the steps that set them, the interval's step count and the
-        spec (npz: arrays ext_val, ext_when, ext_steps, ext_spec; netCDF:
-        ncio.write_state's extremes)."""
+        """The interval so far travels with the state (output.OutputBlock.carried;
+        a producer's `npz` names its npz arrays, `nc` ncio.write_state's keyword):
+        accumulation's accumulators, beginning storage and step count; the running
+        extremes, the steps that set them, the interval's step count and the spec."""
         self.ranges.join()
-        accum = self.accum.state() if self.accum is not None else None
-        ext = self.extremes.state() if self.extremes is not None else None
+        carried = [(p, p.state()) for p in self.block.carried]
         if path.endswith(".nc"):
-            if accum is not None:
-                accum = (self.to_grid_order(accum[0]), self.to_grid_order(accum[1]), accum[2])
-            if ext is not None:
-                ext = (self.to_grid_order(ext[0]), self.to_grid_order(ext[1]), ext[2], ext[3])
+            kw = {p.nc[0]: tuple(self.to_grid_order(v) if isinstance(v, np.ndarray) else v
+                                 for v in st) for p, st in carried}
             ncio.write_state(path, self.grid, self.to_grid_order(self.cs.state.cpu().numpy()),
                              self.to_grid_order(self.cs.isnow.cpu().numpy()), self.t,
-                             self.step_index, accum=accum, extremes=ext)
+                             self.step_index, **kw)
             return
-        extra = {} if accum is None else dict(acc=accum[0], stor_beg=accum[1],
-                                              acc_steps=np.int64(accum[2]))
-        if ext is not None:
-            extra.update(ext_val=ext[0], ext_when=ext[1], ext_steps=np.int64(ext[2]),
-                         ext_spec=np.array(ext[3]))
+        extra = {k: np.int64(v) if isinstance(v, int) else np.asarray(v)
+                 for p, st in carried for k, v in zip(p.npz, st)}
         np.savez(path, **extra, time=np.array(self.t.isoformat()), step=np.int64(self.step_index),
                  state=self.cs.state.cpu().numpy(), isnow=self.cs.isnow.cpu().numpy(),
                  static_f=self.cs.static_f.cpu().numpy(), static_i=self.cs.static_i.cpu().numpy(),
@@ -483,10 +457,8 @@ class OfflineDriver:
             self.cs.state.copy_(torch.as_tensor(np.ascontiguousarray(st[:, idx]),
                                                 device=self.dev))
             self.cs.isnow.copy_(torch.as_tensor(np.ascontiguousarray(isn[idx]), device=self.dev))
-            if self.accum is not None:
-                self.accum.restore(ncio.read_accum(path, self.grid), idx)
-            if self.extremes is not None:
-                self.extremes.restore(ncio.read_extremes(path, self.grid), idx)
+            for p in self.block.carried:
+                p.restore(p.nc[1](path, self.grid), idx)
             self._start = (self.t, self.step_index)
             return
         with np.load(path, allow_pickle=False) as z:
@@ -496,12 +468,8 @@ class OfflineDriver:
             self.t = datetime.datetime.fromisoformat(str(z["time"]))
             self.step_index = int(z["step"])
             self.zsoil = [float(v) for v in z["zsoil"]]
-            if self.accum is not None:
-                self.accum.restore((z["acc"], z["stor_beg"], int(z["acc_steps"]))
-                                   if "acc" in z.files else None)
-            if self.extremes is not None:
-                self.extremes.restore((z["ext_val"], z["ext_when"], int(z["ext_steps"]),
-                                       str(z["ext_spec"])) if "ext_val" in z.files else None)
+            for p in self.block.carried:
+                p.restore(tuple(z[k] for k in p.npz) if p.npz[0] in z.files else None)
         self._start = (self.t, self.step_index)
 
     # ---- time loop -----------------------------------------------------------------
@@ -547,26 +515,9 @@ class OfflineDriver:
                 diag = self.gather.local(b)
             if out and self._diag_free is not None:
                 after = after + (self._diag_free,)  # the output stream's last read of `diag`
-            dstep, level, post = None, L.DIAG_NONE, None
-            if out:
-                dstep, level = diag, L.DIAG_OUT_LEVEL
-                if self.state_mask or self.next:
-                    dstep = diag[:L.NDIAG_OUT]
-            if self.accum is not None:  # every step writes its fluxes
-                level = L.DIAG_OUT_LEVEL
-                dstep, post = self.accum.step(f, diag, out)
-            ext = self.extremes
-            if ext is not None:
-                if ext.need_diag and dstep is None:
-                    # a step between output steps, no accumulation: its fluxes
-                    # go to the extremes' own scratch block
-                    dstep, level = ext.scratch, L.DIAG_OUT_LEVEL
-                post = ext.step(f, dstep if ext.need_diag else None,
-                                diag[self.nflux:self.nflux + self.next] if out else None, post)
-            if out and self.state_mask:
-                post = self._state_post(diag[self.nflux + self.next:], post)
+            dstep, level, post = self.block.plan(f, diag, out)
             if self._veg_table is not None:
-                pre = self._veg_pre(t0, pre)
+                pre = chain((self._veg_pre(t0), pre))
             self.ranges.step(f, self.zsoil, self.dt, timeman.julian(t0), timeman.yearlen(t0.year),
                              dstep, level, after=after, pre=pre, post=post)
             self.feed.launched(t0, self.ranges.producers)
@@ -587,34 +538,20 @@ class OfflineDriver:
         self.flush_output()
         return self
 
-    def _veg_pre(self, t0: datetime.datetime, first):
-        """StreamShards.step's `pre` of a step that starts at t0 with veg_clim:
-        `first` (the feed's, or None) as it is while SHDFAC stands for the
-        step's instant; else the range's columns of the row for that instant,
-        then `first`."""
+    def _veg_pre(self, t0: datetime.datetime):
+        """What a step that starts at t0 with veg_clim puts ahead of the feed's
+        `pre`: nothing while SHDFAC stands for the step's instant, else the
+        range's columns of the row for that instant."""
         when = vegclim.quantise(t0, self.veg_clim)
         if when == self._veg_key:
-            return first
+            return None
         self._veg_key = when
         m0, m1, w = vegclim.month_weights(when)
         row = self.cs.static_f[L.STATIC_F.index("SHDFAC")]
 
         def pre(st, rng):
             self.engine.static_monthly(self._veg_table, m0, m1, w, row, stream=st, cols=rng)
-            if first is not None:
-                first(st, rng)
         return pre
-
-    def _state_post(self, rows: torch.Tensor, first):
-        """StreamShards.step's `post` of an output step with state output:
-        `first` (the accumulation's, or None), then the range's columns of the
-        state rows -- the block's trailing rows -- from the state the step left."""
-        def post(st, rng):
-            if first is not None:
-                first(st, rng)
-            self.engine.state_output(self.cs, self.state_mask, rows, float(ncio.FILL), stream=st,
-                                     cols=rng)
-        return post
 
     def _output_step(self, t1: datetime.datetime, b, rank: int):
         """Hand the output step's block to the writer: the gathered one
@@ -747,10 +684,8 @@ class OfflineDriver:
         self.ranges.join()
         self.t, self.step_index = self._start
         self.feed.reset()   # resident blocks and read-ahead belong to the old time
-        if self.accum is not None:
-            self.accum.restore(None)
-        if self.extremes is not None:
-            self.extremes.restore(None)
+        for p in self.block.carried:
+            p.restore(None)
 
     def _spinup_record(self, k: int, res, tol_arr):
         """The loop's record from this rank's reduction; under a process group
@@ -790,14 +725,11 @@ class OfflineDriver:
     def _write_drift_map(self, drift: torch.Tensor):
         """The drift rows on the grid (nmp_ldasout_grid) under the LDASOUT
         header, stamped with the run's start time."""
-        idx = np.asarray(self.grid.index)
-        point = torch.as_tensor((idx if self.perm is None else idx[self.perm]).astype(np.int32),
-                                device=self.dev)
         npts = self.grid.shape[0] * self.grid.shape[1]
         f32 = self.dtype == torch.float32
         out = torch.empty((L.NDRIFT, npts), device=self.dev,
                           dtype=torch.int32 if f32 else torch.int64)
-        self.engine.ldasout_grid(drift, point, out, float(ncio.FILL))
+        self.engine.ldasout_grid(drift, self.output.point(), out, float(ncio.FILL))
         a = out.cpu().numpy()
         os.makedirs(self.cfg.outdir, exist_ok=True)
         ncio.write_ldasout_grids(os.path.join(self.cfg.outdir, "SPINUP_DRIFT_DOMAIN1"), self.grid,

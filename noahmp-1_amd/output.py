@@ -1,7 +1,19 @@
-"""The output side of the offline driver (driver.OfflineDriver):
-`OutputWriter` stages an output step's fields and writes its files on
-background threads, `Accumulation` adds the steps' fluxes up over each output
-interval on the device."""
+"""The output side of the offline driver (driver.OfflineDriver).
+
+An output file's rows come from producers with one interface, as the forcing
+comes from feeds (feeds._Feed): `Fluxes`, `Accumulation`, `Extremes`, `StateRows`.
+A producer has `names` (its rows), `needs_fluxes` (does it read the step's 16
+fluxes on every step) and `step(f, fluxes, rows)`: one more step with the
+forcing `f`, its fluxes in `fluxes` (None unless `needs_fluxes`) and, at an
+output step, `rows`, the producer's slice of the output block (else None).  It
+returns the hook `hook(stream, (lo, hi))` that enqueues the producer's kernels
+for a column range after the step, or None.  One that carries an interval also
+has `state()`, `restore(state | None, idx)`, `npz` (its npz items, in state()'s
+order) and `nc` (ncio.write_state's keyword, the function that reads it back).
+
+`OutputBlock` composes a run's producers: the rows' layout, the one scratch
+block and each step's plan.  `OutputWriter` stages an output step's block and
+writes its files on background threads."""
 from __future__ import annotations
 
 import datetime
@@ -10,7 +22,20 @@ from concurrent.futures import ThreadPoolExecutor
 import numpy as np
 import torch
 
-from . import layout as L, ncio
+from . import extremes as X, layout as L, ncio, stateout
+
+
+def chain(hooks):
+    """One StreamShards hook `hook(stream, (lo, hi))` from several, None among
+    them: none is None, one is itself, more are called in order."""
+    hooks = [h for h in hooks if h is not None]
+    if len(hooks) < 2:
+        return hooks[0] if hooks else None
+
+    def hook(st, rng):
+        for h in hooks:
+            h(st, rng)
+    return hook
 
 
 class OutputWriter:
@@ -19,6 +44,9 @@ class OutputWriter:
     (nmp_ldasout_grid) and copied on a stream of its own and written by writer
     threads (ncio.write_ldasout_grids).
 
+    block: the run's OutputBlock -- the rows' names, and `region_rows`, the
+    leading rows the regions reduce (None: all of them; a run with state
+    output leaves out its trailing rows, which can hold the fill value).
     `stage` (the rank that writes, in a run that writes output) allocates the
     staging buffers up front: a page-locked allocation of the whole set's
     fluxes costs tens of ms inside the time loop (the file's grids in its byte
@@ -28,17 +56,13 @@ class OutputWriter:
     # file's write is a memory copy into the page cache on its own thread
     OUT_WRITERS, OUT_BUFFERS = 2, 3
 
-    def __init__(self, engine, cfg, grid, out_names, ncol_total: int, dtype, dev, stage: bool,
-                 region_plan=None, write_grids: bool = True, perm=None,
-                 region_rows: int | None = None):
-        """region_rows: the block's leading rows the regions reduce (default:
-        all of them); a run with state output leaves out its trailing rows,
-        which can hold the fill value."""
-        self.engine, self.cfg, self.grid, self.out_names = engine, cfg, grid, out_names
+    def __init__(self, engine, cfg, grid, block, ncol_total: int, dtype, dev, stage: bool,
+                 region_plan=None, write_grids: bool = True, perm=None):
+        self.engine, self.cfg, self.grid, self.out_names = engine, cfg, grid, block.names
         self.dev, self.region_plan, self.write_grids, self.perm = dev, region_plan, write_grids, perm
         self.written, self.regions_written = [], []
-        nout = len(out_names)
-        self.region_rows = nout if region_rows is None else int(region_rows)
+        nout = len(self.out_names)
+        self.region_rows = nout if block.region_rows is None else block.region_rows
         self._writer = ThreadPoolExecutor(self.OUT_WRITERS)
         self._out_host = [None] * self.OUT_BUFFERS
         if stage and write_grids:
@@ -49,7 +73,7 @@ class OutputWriter:
             self._out_host = [torch.empty(shape, dtype=dtype, pin_memory=True)
                               for _ in range(self.OUT_BUFFERS)]
         self._out_fut, self._n_out_w = [None] * self.OUT_BUFFERS, 0
-        # the columns' grid points and the device grids, from the first output step on
+        # the columns' grid points and the device grids, from their first use on
         self._out_point, self._out_dev = None, None
         self._reg_dev, self._reg_host = None, [None] * self.OUT_BUFFERS
         if region_plan is not None:
@@ -60,19 +84,25 @@ class OutputWriter:
                                           dtype=torch.float64,
                                           pin_memory=True) for _ in range(self.OUT_BUFFERS)]
 
-    def _grids(self, d: torch.Tensor, stream) -> torch.Tensor:
-        """d laid on the file's grids in its byte order, on `stream`."""
+    def point(self) -> torch.Tensor:
+        """The grid point of every engine column (int32, on the device)."""
         if self._out_point is None:
             idx = np.asarray(self.grid.index)
             self._out_point = torch.as_tensor(
                 (idx if self.perm is None else idx[self.perm]).astype(np.int32), device=self.dev)
+        return self._out_point
+
+    def _grids(self, d: torch.Tensor, stream) -> torch.Tensor:
+        """d laid on the file's grids in its byte order, on `stream`."""
+        point = self.point()
+        if self._out_dev is None:
             npts = self.grid.shape[0] * self.grid.shape[1]
             self._out_dev = torch.empty((d.shape[0], npts), device=self.dev,
                                         dtype=torch.int32 if d.dtype == torch.float32
                                         else torch.int64)
         # (nmp_ldasout_grid takes at most NDIAG_FULL rows a call)
         for r in range(0, d.shape[0], L.NDIAG_FULL):
-            self.engine.ldasout_grid(d[r:r + L.NDIAG_FULL], self._out_point,
+            self.engine.ldasout_grid(d[r:r + L.NDIAG_FULL], point,
                                      self._out_dev[r:r + L.NDIAG_FULL], float(ncio.FILL),
                                      stream=stream)
         return self._out_dev
@@ -141,28 +171,85 @@ class OutputWriter:
                 f.result()
 
 
+class Fluxes:
+    """The output step's 16 surface fluxes: the step kernel writes them into
+    their rows itself, so there is nothing to enqueue after it."""
+    names, needs_fluxes = L.DIAG_OUT, False
+
+    def step(self, f, fluxes, rows):
+        return None
+
+
+class Accumulation:
+    """An output interval's accumulated output (layout.BUDGET), on the device:
+    the accumulators `acc` (every step's fluxes are added up), the water storage
+    at the interval's beginning and end, and `steps`, the steps added up so far."""
+    names, needs_fluxes = L.BUDGET, True
+    npz, nc = ("acc", "stor_beg", "acc_steps"), ("accum", ncio.read_accum)
+
+    def __init__(self, engine, cs, dt: float):
+        self.engine, self.cs, self.dt = engine, cs, dt
+        n, dev, dtype = cs.ncol, cs.state.device, cs.state.dtype
+        self.acc = torch.zeros((L.NACC, n), dtype=torch.float64, device=dev)
+        self.stor_beg = torch.zeros(n, dtype=dtype, device=dev)
+        self.stor_end = torch.zeros(n, dtype=dtype, device=dev)
+        self.restore(None)
+
+    def state(self):
+        """(acc, stor_beg, steps) of the interval so far, on the host: what a restart carries."""
+        return self.acc.cpu().numpy(), self.stor_beg.cpu().numpy(), self.steps
+
+    def restore(self, state, idx=slice(None)):
+        """`state` (state(), of the columns `idx` picks) resumes its interval;
+        None starts a fresh one: zero accumulators, the beginning storage from
+        the model state as it is (nmp_water_storage, on the current stream)."""
+        if state is None:
+            self.steps = 0
+            self.acc.zero_()
+            self.engine.water_storage(self.cs, self.stor_beg)
+            return
+        dev = self.acc.device
+        self.acc.copy_(torch.as_tensor(np.ascontiguousarray(state[0][:, idx], np.float64),
+                                       device=dev))
+        self.stor_beg.copy_(torch.as_tensor(np.ascontiguousarray(state[1][idx]), device=dev))
+        self.steps = int(state[2])
+
+    def step(self, f, fluxes, rows):
+        """Add the step's fluxes and precipitation to the accumulators; at an
+        output step (rows: the output block's budget rows) also close the
+        interval, and the next step begins a new one."""
+        self.steps += 1
+        span_s = self.steps * self.dt
+        if rows is not None:
+            self.steps = 0
+
+        def hook(st, rng):
+            self.engine.accumulate(fluxes, f, self.acc, self.dt, stream=st, cols=rng)
+            if rows is not None:
+                self.engine.water_storage(self.cs, self.stor_end, stream=st, cols=rng)
+                self.engine.accum_finish(self.acc, self.stor_end, self.stor_beg, rows, span_s,
+                                         stream=st, cols=rng)
+        return hook
+
+
 class Extremes:
     """An output interval's extremes (extremes.py), on the device: the running
     maxima and minima `val` of the selected series, `when` (the step of the
-    interval that set each) and `k`, the steps taken so far.  Only with a
-    series of the output fluxes, and only when no accumulation lends its own,
-    a scratch block `scratch` for the fluxes of the steps between output
-    steps."""
+    interval that set each) and `k`, the steps taken so far.  Only a series of
+    the output fluxes makes every step write them (`need_diag`)."""
+    npz, nc = ("ext_val", "ext_when", "ext_steps", "ext_spec"), ("extremes", ncio.read_extremes)
 
-    def __init__(self, engine, cs, series, dt: float, scratch: bool):
-        from . import extremes as X
+    def __init__(self, engine, cs, series, dt: float):
         self.engine, self.cs, self.dt, self.series = engine, cs, dt, list(series)
         self.spec = X.spec_string(self.series)
         self.kind_rows, self.stats = X.pairs(self.series), X.masks(self.series)
-        self.names, self.need_diag = X.row_names(self.series), X.has_diag(self.series)
+        self.names = X.row_names(self.series)
+        self.needs_fluxes = self.need_diag = X.has_diag(self.series)
         self.need_state = any(s.kind == L.EXT_SRC_STATE for s in self.series)
         self.need_forcing = any(s.kind == L.EXT_SRC_FORCING for s in self.series)
         n, dev, dtype = cs.ncol, cs.state.device, cs.state.dtype
         self.val = torch.zeros((2 * len(self.series), n), dtype=dtype, device=dev)
         self.when = torch.zeros((2 * len(self.series), n), dtype=torch.int32, device=dev)
-        self.scratch = None
-        if scratch and self.need_diag:
-            self.scratch = torch.zeros((L.NDIAG_OUT, n), dtype=dtype, device=dev)
         self.k = 0
 
     def state(self):
@@ -183,13 +270,11 @@ class Extremes:
                                         device=dev))
         self.k = int(state[2])
 
-    def step(self, f, fluxes, rows, first):
-        """One more step: StreamShards.step's `post` -- `first` (the
-        accumulation's, or None), then this step into the running extremes
-        from its fluxes block `fluxes` (None without a flux series), its
-        forcing `f` and the state it left; at an output step (rows: the output
-        block's extremes rows) also the interval's rows, and the next step
-        begins a new interval."""
+    def step(self, f, fluxes, rows):
+        """Fold this step into the running extremes from its fluxes (None
+        without a flux series), its forcing `f` and the state it left; at an
+        output step (rows: the output block's extremes rows) also form the
+        interval's rows, and the next step begins a new interval."""
         self.k += 1
         k = self.k
         if rows is not None:
@@ -197,78 +282,69 @@ class Extremes:
         state = self.cs.state if self.need_state else None
         forcing = f if self.need_forcing else None
 
-        def post(st, rng):
-            if first is not None:
-                first(st, rng)
+        def hook(st, rng):
             self.engine.extremes_update(self.kind_rows, k, self.val, self.when, fluxes, forcing,
                                         state, stream=st, cols=rng)
             if rows is not None:
                 self.engine.extremes_output(self.stats, self.dt, self.val, self.when, rows,
                                             stream=st, cols=rng)
-        return post
+        return hook
 
 
-class Accumulation:
-    """An output interval's accumulated output (layout.BUDGET), on the device:
-    the accumulators `acc`, the scratch block `acc_diag` for the fluxes of the
-    steps between output steps (every step writes them), the water storage at
-    the interval's beginning and end, and `steps`, the steps added up so far."""
+class StateRows:
+    """The selected groups of the land state (layout.STATE_OUT), formed at
+    output steps from the state the step left (nmp_state_output), the groups
+    that can hold the fill value last: `nofill_rows` come before them."""
+    needs_fluxes = False
 
-    def __init__(self, engine, cs, dt: float):
-        self.engine, self.cs, self.dt = engine, cs, dt
+    def __init__(self, engine, cs, mask: int):
+        self.engine, self.cs, self.mask = engine, cs, mask
+        self.names, self.nofill_rows = stateout.row_names(mask), stateout.nofill_rows(mask)
+
+    def step(self, f, fluxes, rows):
+        if rows is None:
+            return None
+
+        def hook(st, rng):
+            self.engine.state_output(self.cs, self.mask, rows, float(ncio.FILL), stream=st,
+                                     cols=rng)
+        return hook
+
+
+class OutputBlock:
+    """A run's producers in row order (fluxes, budget rows, extremes rows, state
+    rows) and what each step owes them.  `diag` is the (rows, ncol) block,
+    `region_rows` the leading rows the regions reduce (None = all; state output
+    ends them before the groups that can hold the fill value), `scratch` the one
+    block the steps between output steps write their fluxes to (None unless a
+    producer reads them), `carried` the producers a restart carries."""
+
+    def __init__(self, engine, cs, dt: float, accumulate: bool, ext_series, state_mask: int):
+        self.accum = Accumulation(engine, cs, dt) if accumulate else None
+        self.extremes = Extremes(engine, cs, ext_series, dt) if ext_series is not None else None
+        state = StateRows(engine, cs, state_mask) if state_mask else None
+        self.producers = [p for p in (Fluxes(), self.accum, self.extremes, state) if p is not None]
+        self.carried = [p for p in (self.accum, self.extremes) if p is not None]
+        self.names, self.slices = [], []
+        for p in self.producers:
+            self.slices.append(slice(len(self.names), len(self.names) + len(p.names)))
+            self.names += p.names
+        self.region_rows = None if state is None else self.slices[-1].start + state.nofill_rows
         n, dev, dtype = cs.ncol, cs.state.device, cs.state.dtype
-        self.acc = torch.zeros((L.NACC, n), dtype=torch.float64, device=dev)
-        self.acc_diag = torch.zeros((L.NDIAG_OUT, n), dtype=dtype, device=dev)
-        self.stor_beg = torch.zeros(n, dtype=dtype, device=dev)
-        self.stor_end = torch.zeros(n, dtype=dtype, device=dev)
-        self.start()
+        self.diag = torch.zeros((len(self.names), n), dtype=dtype, device=dev)
+        self.scratch = torch.zeros((L.NDIAG_OUT, n), dtype=dtype, device=dev) \
+            if any(p.needs_fluxes for p in self.producers) else None
 
-    def start(self, acc=None, stor_beg=None, steps: int = 0):
-        """The accumulation state of an output interval: fresh (zero
-        accumulators, the beginning storage formed from the state as it is,
-        nmp_water_storage) or, part way through one, what a restart carried.
-        On the current stream, which the ranges' next step waits for."""
-        self.steps = int(steps)
-        if acc is None:
-            self.acc.zero_()
-            self.engine.water_storage(self.cs, self.stor_beg)
-            return
-        dev = self.acc.device
-        self.acc.copy_(torch.as_tensor(np.ascontiguousarray(acc, np.float64), device=dev))
-        self.stor_beg.copy_(torch.as_tensor(np.ascontiguousarray(stor_beg), device=dev))
-
-    def state(self):
-        """(acc, stor_beg, steps) of the interval so far, on the host: what a restart carries."""
-        return self.acc.cpu().numpy(), self.stor_beg.cpu().numpy(), self.steps
-
-    def restore(self, state, idx=slice(None)):
-        """`state` (state(), of the columns `idx` picks) resumes its interval;
-        None starts a fresh one from the model state as it is."""
-        if state is None:
-            self.start()
-        else:
-            self.start(state[0][:, idx], state[1][idx], state[2])
-
-    def step(self, f, diag, out: bool):
-        """One more step: (the block its fluxes go to, StreamShards.step's
-        `post`).  The output step's go into rows 0..15 of the output block
-        `diag`, the others' into the scratch block."""
-        fluxes = diag[:L.NDIAG_OUT] if out else self.acc_diag
-        self.steps += 1
-        post = self.post(fluxes, f, diag[L.NDIAG_OUT:L.NDIAG_OUT + L.NBUDGET] if out else None,
-                         self.steps * self.dt)
+    def plan(self, f, diag, out: bool):
+        """One more step with the forcing `f`: (where it writes its fluxes, its
+        diag_level, StreamShards.step's `post`).  An output step (`out`) writes
+        them into rows 0..15 of `diag` (the block, or a process group's gather
+        buffer), another into the scratch block, or nowhere (DIAG_NONE)."""
+        fluxes, level = None, L.DIAG_NONE
         if out:
-            self.steps = 0
-        return fluxes, post
-
-    def post(self, fluxes, forcing, budget, span_s):
-        """StreamShards.step's `post` of an accumulating step: add the step's
-        fluxes and precipitation to the accumulators; at an output step
-        (budget: the output block's rows 16..34) also close the interval."""
-        def post(st, rng):
-            self.engine.accumulate(fluxes, forcing, self.acc, self.dt, stream=st, cols=rng)
-            if budget is not None:
-                self.engine.water_storage(self.cs, self.stor_end, stream=st, cols=rng)
-                self.engine.accum_finish(self.acc, self.stor_end, self.stor_beg, budget, span_s,
-                                         stream=st, cols=rng)
-        return post
+            fluxes, level = diag[:L.NDIAG_OUT], L.DIAG_OUT_LEVEL
+        elif self.scratch is not None:
+            fluxes, level = self.scratch, L.DIAG_OUT_LEVEL
+        return fluxes, level, chain(
+            p.step(f, fluxes if p.needs_fluxes else None, diag[s] if out else None)
+            for p, s in zip(self.producers, self.slices))

@@ -406,7 +406,7 @@ def test_steps_between_outputs_keep_their_diag_level(engine_lib, traj, tmp_path)
     # state and forcing series only: the steps between output steps write no fluxes
     drv = driver.OfflineDriver(_cfg(tmp_path, "sf"), _cols(traj), forcing=ff,
                                extremes="PRCP:max+tmax,TG,SNEQV,SMC1,STC1")
-    assert drv.extremes.scratch is None and not drv.extremes.need_diag
+    assert drv.block.scratch is None and not drv.extremes.need_diag
     calls = _record_steps(drv)
     drv.run(nsteps=25)
     drv.engine.close()
@@ -416,17 +416,17 @@ def test_steps_between_outputs_keep_their_diag_level(engine_lib, traj, tmp_path)
     drv = driver.OfflineDriver(_cfg(tmp_path, "d"), _cols(traj), forcing=ff, extremes="FSH,TG")
     calls = _record_steps(drv)
     drv.run(nsteps=25)
-    scratch, block = drv.extremes.scratch.data_ptr(), drv.diag.data_ptr()
+    scratch, block = drv.block.scratch.data_ptr(), drv.diag.data_ptr()
     drv.engine.close()
     assert [c[0] for c in calls] == [L.DIAG_OUT_LEVEL] * 25
     assert [c[1] for c in calls] == ([scratch] * 11 + [block]) * 2 + [scratch]
     # with accumulation the scratch block is accumulation's: one every-step flux write
     drv = driver.OfflineDriver(_cfg(tmp_path, "da"), _cols(traj), forcing=ff, extremes="FSH,TG",
                                accumulate=True)
-    assert drv.extremes.scratch is None
+    assert not hasattr(drv.extremes, "scratch") and not hasattr(drv.accum, "acc_diag")
     calls = _record_steps(drv)
     drv.run(nsteps=25)
-    scratch, block = drv.accum.acc_diag.data_ptr(), drv.diag.data_ptr()
+    scratch, block = drv.block.scratch.data_ptr(), drv.diag.data_ptr()
     drv.engine.close()
     assert [c[0] for c in calls] == [L.DIAG_OUT_LEVEL] * 25
     assert [c[1] for c in calls] == ([scratch] * 11 + [block]) * 2 + [scratch]
