@@ -870,6 +870,85 @@ int nmp_extremes_output(nmp_engine* eng, int64_t ncol, int nseries, const int32_
                         double dt, const void* val, const int32_t* when, int64_t ld_ext,
                         void* out, int64_t ld_out, void* stream);
 
+/* Interval statistics (no counterpart in the reference, which writes no
+ * output): over an output interval, the mean of a per-column series, or -- for
+ * a series with a condition -- how long the condition held, the longest
+ * unbroken spell of it and the value-seconds beyond its threshold: a day's
+ * mean soil moisture, its frost hours, its longest wet spell, its growing
+ * degree-days.
+ *
+ * Items.  An item is a series with either nothing or a condition attached.
+ * The series is a (kind, row) pair as in "Interval extremes" (NMP_EXT_SRC_DIAG,
+ * NMP_EXT_SRC_FORCING, NMP_EXT_SRC_STATE; the three blocks share the leading
+ * dimension ld).  The condition is an operator NMP_IST_GT, _GE, _LT or _LE and
+ * a threshold c; NMP_IST_NONE makes a mean item.  `items` is a HOST array of
+ * four words per item: items[4*i] = kind, [4*i + 1] = row, [4*i + 2] = operator,
+ * [4*i + 3] = the mask of the item's output rows, NMP_IST_MEAN for a mean item
+ * and any of NMP_IST_DUR, NMP_IST_DEG, NMP_IST_SPELL for a conditioned one;
+ * 1 <= nitems <= NMP_IST_MAXITEMS.  `thresholds` is a HOST array of nitems
+ * doubles (a mean item's is not read).
+ *
+ * Resident state, leading dimension ld_st: `acc`, nitems x ld_st doubles in
+ * both engine precisions, row i the running sum of item i; `cnt`, 3*nitems x
+ * ld_st int32, row 3*i the steps the condition held (count), row 3*i + 1 the
+ * current run, row 3*i + 2 the longest run.  A mean item never touches its
+ * cnt rows.
+ *
+ * nmp_intstats_update: one kernel.  k >= 1 is the number of this step within
+ * its interval.  Per column and item, with v the series' value as loaded (the
+ * engine precision T) and cT the threshold rounded to T, the rule is part of
+ * this interface:
+ *   k == 1:  the old acc and cnt are not read: they count as +0.0 and 0.  No
+ *            reset launch exists or is needed; stale or NaN contents are
+ *            harmless.
+ *   mean item:         acc = acc + (double)v, one double add per step.
+ *   conditioned item:  h = v OP cT, compared in T: a NaN never holds, -0 and
+ *            +0 compare equal.  If h: acc = acc + d with d = (double)v -
+ *            (double)cT for GT and GE, d = (double)cT - (double)v for LT and
+ *            LE; count += 1; run += 1; longest = max(longest, run).  Otherwise
+ *            run = 0 and nothing else changes.
+ * A store that would write the value already there may be skipped; at k == 1
+ * every row of the item is written.  A NaN the sum forms itself (inf + -inf
+ * in a mean) is the adder's default quiet NaN, sign bit set, on the device as
+ * on an x86 host; a NaN operand travels quieted with its payload.  diag may be NULL when no item has kind
+ * DIAG; the same holds for forcing and for state.
+ *
+ * nmp_intstats_output: one kernel.  k is the interval's step count, dt the
+ * step in seconds.  It takes the same `items` and writes the rows of `out`
+ * (leading dimension ld_out, engine precision) in item order and within an
+ * item in bit order MEAN, DUR, DEG, SPELL, for the bits that are set:
+ *   MEAN   (T)(acc / (double)k)       one IEEE double division, one conversion
+ *   DUR    (T)((double)count * dt)    seconds the condition held
+ *   DEG    (T)(acc * dt)              value-seconds beyond the threshold
+ *   SPELL  (T)((double)longest * dt)  seconds of the longest unbroken spell
+ * It changes neither acc nor cnt.  Only the operations listed are performed,
+ * in the stated order, and nothing in them can be contracted.
+ *
+ * Both: device pointers, possibly offset by a range's first column; one lane
+ * per column, enqueued on `stream`; the calls neither synchronise nor
+ * allocate; elements ncol.. of every row, and rows not named, are untouched
+ * (noahmp-1_amd/intstats.py update_host / output_host restate both in numpy,
+ * bit for bit).  NMP_E_ARG, with nothing enqueued, first for a NULL engine,
+ * ncol < 0, ld, ld_st or ld_out below ncol or at or above 2^29; then for
+ * nitems outside 1..NMP_IST_MAXITEMS, a NULL items or thresholds, a kind
+ * outside the three, a row outside its block, an operator outside the five, a
+ * mask of 0 or with a bit above NMP_IST_SPELL, a mean item with another bit
+ * than MEAN or a conditioned one with MEAN, a conditioned item's threshold
+ * that is not finite, k < 1, dt not finite or <= 0; then ncol == 0 is NMP_OK
+ * with nothing enqueued; then -- with ncol > 0 -- for a NULL acc or out, a
+ * NULL cnt with a conditioned item, or a NULL block that a named item needs. */
+#define NMP_IST_MAXITEMS 32
+enum { NMP_IST_NONE = 0, NMP_IST_GT = 1, NMP_IST_GE = 2, NMP_IST_LT = 3, NMP_IST_LE = 4 };
+enum { NMP_IST_MEAN = 1, NMP_IST_DUR = 2, NMP_IST_DEG = 4, NMP_IST_SPELL = 8 };
+int nmp_intstats_update(nmp_engine* eng, int64_t ncol, int64_t ld, int nitems,
+                        const int32_t* items, const double* thresholds,
+                        const void* diag /* may be NULL */, const void* forcing /* may be NULL */,
+                        const void* state /* may be NULL */, int32_t k, double* acc, int32_t* cnt,
+                        int64_t ld_st, void* stream);
+int nmp_intstats_output(nmp_engine* eng, int64_t ncol, int nitems, const int32_t* items,
+                        int32_t k, double dt, const double* acc, const int32_t* cnt,
+                        int64_t ld_st, void* out, int64_t ld_out, void* stream);
+
 int nmp_run(nmp_engine* eng, int64_t ncol, int64_t ld, const float zsoil[4], float dt,
             float julian0, int32_t yearlen, int32_t nsteps, void* state, int32_t* isnow,
             const void* static_f, const int32_t* static_i, const void* forcing,

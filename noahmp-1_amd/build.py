@@ -18,7 +18,7 @@ DEFAULT_LIB_PATH = os.path.join(LIB_DIR, "libnoahmp_engine.so")
 # NOAHMP_ENGINE_LIB: a tuning variant (tools/build_variants.py), hash-checked only on request
 LIB_PATH = os.environ.get("NOAHMP_ENGINE_LIB") or DEFAULT_LIB_PATH
 SOURCES = ["engine.hip", "sflx_kernel.hip", "sflx_kernel_f64.hip", "sflx_kernel_f64s.hip",
-           "rebin.hip", "forcing.hip", "regrid.hip", "interp.hip", "accum.hip", "regions.hip", "stateout.hip", "drift.hip", "vegclim.hip", "extremes.hip", "routines.hip", "tables.cpp"]
+           "rebin.hip", "forcing.hip", "regrid.hip", "interp.hip", "accum.hip", "regions.hip", "stateout.hip", "drift.hip", "vegclim.hip", "extremes.hip", "intstats.hip", "routines.hip", "tables.cpp"]
 HEADERS = ["dev_params.h", "sflx_kargs.h", "sflx_math.h", "sflx_routines.h", "glibc_math.h",
            "vege_domain.h", "engine_impl.h", "col_math.h"]
 # per-source flags: sflx_kernel.hip is compiled as the fp32 translation unit,

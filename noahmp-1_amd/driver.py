@@ -25,6 +25,11 @@ offline/noahmp_config.py has no time loop, forcing reader or writer, SURVEY
   selected series -- their maximum, their minimum and the time each occurred
   (extremes.py), tracked on the device after every step (nmp_extremes_update /
   nmp_extremes_output);
+  with ``interval_stats`` each file also carries the interval's means of the
+  selected series and, for series with a condition, the time the condition
+  held, its longest spell and the value-seconds beyond its threshold
+  (intstats.py), added up on the device after every step (nmp_intstats_update /
+  nmp_intstats_output);
   with ``veg_clim`` the vegetation fraction SHDFAC follows the static file's
   monthly GREENFRAC climatology through the run, re-formed on the device from
   the resident table (nmp_static_monthly; vegclim.py states the scheme) instead
@@ -65,7 +70,8 @@ import numpy as np
 import torch
 import torch.distributed as dist
 
-from . import cases, extremes as xtr, layout as L, ncio, shard, stateout, timeman, vegclim
+from . import (cases, extremes as xtr, intstats as ist, layout as L, ncio, shard, stateout,
+               timeman, vegclim)
 from .config import Config
 from .engine import ColumnState, Engine, StreamShards
 from .feeds import (DeviceSyntheticForcing, ForcingUpload, HostFeed,  # noqa: F401  (re-exported)
@@ -140,7 +146,7 @@ class OfflineDriver:
                  downscale: bool = False, lapse_rate: float = 0.0065, interp: bool = False,
                  hold=("RAINRATE",), sw_zenith: bool = True, cosz_floor: float = 0.05,
                  prefetch: bool = True, state_out=None, veg_clim: str | None = None,
-                 greenfrac=None, extremes=None):
+                 greenfrac=None, extremes=None, interval_stats=None):
         """cols: this rank's columns (all of them on a single rank); under an
         initialised process group they must be the rank's shard_range block of
         the global column set.  ldasin_upload: with a provider that has
@@ -230,7 +236,24 @@ class OfflineDriver:
         too); without one the steps between output steps stay at DIAG_NONE.
         REGIONS files carry the rows; restarts carry the interval so far
         (save_restart).  Refused in a run that writes no output.  None (the
-        default): every code path and output byte is as without it."""
+        default): every code path and output byte is as without it.
+        interval_stats: "T2M,FROST=T2M@lt273.15:dur+spell,GDD=SFCTMP@gt278.15:deg",
+        or an iterable of such items (intstats.parse: the series of `extremes`;
+        without a condition the interval's mean, with gt, ge, lt or le and a
+        threshold, under a label, the time the condition held, its longest
+        unbroken spell and the value-seconds beyond the threshold).  Every step
+        then adds its values to the interval's running sums and counters on
+        each range's stream right after the step (nmp_intstats_update, after
+        accumulation's and extremes' calls), and output steps write the rows
+        <LABEL>_MEAN, _DUR, _DEG, _SPELL (nmp_intstats_output) after the
+        extremes rows and before the state rows.  The interval's step count is
+        the driver's.  With an item of the output fluxes every step writes its
+        fluxes into the one scratch block; without one the steps between output
+        steps stay at DIAG_NONE.  REGIONS files carry the rows; restarts carry
+        the interval so far.  Refused in a run that writes no output, and when
+        a row name occurs twice in the run's output.  None (the default):
+        nothing is allocated or enqueued, every code path and output byte is
+        as without it."""
         # (a bad veg_clim or table is refused before any device work)
         self.veg_clim, gf_host = veg_clim, None
         if veg_clim is not None:
@@ -248,6 +271,11 @@ class OfflineDriver:
             ext_series = xtr.parse(extremes)
             if not write or cfg.output_interval is None:
                 raise ValueError("extremes needs a run that writes output")
+        stat_items = None
+        if interval_stats is not None:
+            stat_items = ist.parse(interval_stats)
+            if not write or cfg.output_interval is None:
+                raise ValueError("interval_stats needs a run that writes output")
         if not write_grids and regions is None:
             raise ValueError("write_grids=False needs regions: the run would write nothing")
         # (a bad cosz, downscale or interp is refused before any device work)
@@ -291,9 +319,9 @@ class OfflineDriver:
         self.accumulate = bool(accumulate)
         # the output rows: their producers, layout and per-step plan (output.OutputBlock)
         block = self.block = OutputBlock(self.engine, self.cs, self.dt, self.accumulate,
-                                         ext_series, self.state_mask)
+                                         ext_series, self.state_mask, stat_items)
         self.out_names, self.diag = block.names, block.diag
-        self.accum, self.extremes = block.accum, block.extremes
+        self.accum, self.extremes, self.intstats = block.accum, block.extremes, block.intstats
         nout = len(self.out_names)
         if nout > L.NDIAG_OUT and grid is not None:
             # a grid whose 35 fields or state rows do not pass the classic
@@ -419,7 +447,8 @@ class OfflineDriver:
         """The interval so far travels with the state (output.OutputBlock.carried;
         a producer's `npz` names its npz arrays, `nc` ncio.write_state's keyword):
         accumulation's accumulators, beginning storage and step count; the running
-        extremes, the steps that set them, the interval's step count and the spec."""
+        extremes, the steps that set them, the interval's step count and the spec;
+        the interval statistics' sums and counters, step count and spec."""
         self.ranges.join()
         carried = [(p, p.state()) for p in self.block.carried]
         if path.endswith(".nc"):
@@ -446,7 +475,8 @@ class OfflineDriver:
         With extremes on, likewise: a restart that carries an interval's
         extremes under this run's spec resumes it; one without them, or with
         another spec, starts a fresh interval here, so the next output's
-        extremes cover the steps from here."""
+        extremes cover the steps from here.  Interval statistics follow the
+        same rule."""
         self.ranges.join()  # no range may still be stepping the state being replaced
         self.feed.reset()   # resident blocks and read-ahead belong to the old time
         self._veg_key = None  # veg_clim: SHDFAC is re-formed for the restart's time

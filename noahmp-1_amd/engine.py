@@ -558,6 +558,59 @@ class Engine:
                    m.ctypes.data_as(C.POINTER(C.c_int32)), float(dt), _ptr(val, lo), _ptr(when, lo),
                    n, _ptr(out_rows, lo), n)
 
+    # ---- interval statistics (nmp_intstats_update / nmp_intstats_output) ---------
+    def intstats_update(self, table, thresholds, k: int, acc: torch.Tensor, cnt: torch.Tensor,
+                        diag: torch.Tensor | None = None, forcing: torch.Tensor | None = None,
+                        state: torch.Tensor | None = None, stream=None,
+                        cols: tuple[int, int] | None = None):
+        """nmp_intstats_update: step k >= 1 of an output interval into the
+        running sums acc (nitems, n) float64 and the counters cnt (3*nitems,
+        n) int32 -- row 3i the steps item i's condition held, 3i + 1 the
+        current run, 3i + 2 the longest run.  table: the items' (kind, row,
+        operator, stat mask) words (intstats.table); thresholds: one double per
+        item (intstats.thresholds); diag (NDIAG_OUT, n), forcing (NFORCING, n)
+        and state (NSTATE, n) are the step's blocks, None where no item names
+        one.  intstats.update_host is the numpy form.  cols=(lo, hi) updates
+        only those columns, enqueued on `stream`."""
+        tab = np.ascontiguousarray(np.asarray(table, np.int32).reshape(-1, 4))
+        thr = np.ascontiguousarray(np.asarray(thresholds, np.float64).reshape(-1))
+        ni, n = int(tab.shape[0]), int(acc.shape[1]) if acc.dim() == 2 else -1
+        assert thr.shape[0] == ni, "one threshold per item"
+        lo, hi = self._cols_range(n, cols)
+        self._check_block(acc, (ni, n), torch.float64, "acc")
+        self._check_block(cnt, (3 * ni, n), torch.int32, "cnt")
+        for t, rows, what in ((diag, L.NDIAG_OUT, "diag"), (forcing, L.NFORCING, "forcing"),
+                              (state, L.NSTATE, "state")):
+            if t is not None:
+                self._check_block(t, (rows, n), self.dtype, what)
+        self._call("nmp_intstats_update", stream, hi - lo, n, ni,
+                   tab.ctypes.data_as(C.POINTER(C.c_int32)),
+                   thr.ctypes.data_as(C.POINTER(C.c_double)), _ptr(diag, lo), _ptr(forcing, lo),
+                   _ptr(state, lo), int(k), _ptr(acc, lo), _ptr(cnt, lo), n)
+
+    def intstats_output(self, table, k: int, dt: float, acc: torch.Tensor, cnt: torch.Tensor,
+                        out_rows: torch.Tensor, stream=None,
+                        cols: tuple[int, int] | None = None):
+        """nmp_intstats_output: the output rows of the items' stat masks (in
+        item order, within an item MEAN, DUR, DEG, SPELL) from acc and cnt
+        after the interval's k steps of dt seconds into out_rows (the masks'
+        bits in all, n), engine precision: (T)(acc / (double)k), (T)((double)
+        count * dt), (T)(acc * dt), (T)((double)longest * dt).  out_rows may
+        be rows of a block (a contiguous row slice).  intstats.output_host is
+        the numpy form.  cols=(lo, hi) writes only those columns, enqueued on
+        `stream`."""
+        tab = np.ascontiguousarray(np.asarray(table, np.int32).reshape(-1, 4))
+        ni, n = int(tab.shape[0]), int(acc.shape[1]) if acc.dim() == 2 else -1
+        lo, hi = self._cols_range(n, cols)
+        self._check_block(acc, (ni, n), torch.float64, "acc")
+        self._check_block(cnt, (3 * ni, n), torch.int32, "cnt")
+        if all(0 < int(x) < 16 for x in tab[:, 3]):   # (the library refuses any other mask)
+            nrow = sum(bin(int(x)).count("1") for x in tab[:, 3])
+            self._check_block(out_rows, (nrow, n), self.dtype, "out_rows")
+        self._call("nmp_intstats_output", stream, hi - lo, ni,
+                   tab.ctypes.data_as(C.POINTER(C.c_int32)), int(k), float(dt), _ptr(acc, lo),
+                   _ptr(cnt, lo), n, _ptr(out_rows, lo), n)
+
     # ---- region-aggregated output (nmp_region_reduce) ---------------------------
     def region_reduce(self, fields: torch.Tensor, plan, sums: torch.Tensor,
                       means: torch.Tensor | None = None, stream=None):

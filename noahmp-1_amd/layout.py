@@ -74,6 +74,15 @@ EXT_MAX, EXT_MIN, EXT_TMAX, EXT_TMIN = 1, 2, 4, 8
 EXT_STATS = {"MAX": EXT_MAX, "MIN": EXT_MIN, "TMAX": EXT_TMAX, "TMIN": EXT_TMIN}
 EXT_MAXSERIES = 32
 
+# interval statistics (nmp_intstats_update / nmp_intstats_output): an item's
+# operator (NMP_IST_NONE = a mean item), the stat bits of its output rows
+# (NMP_IST_*, in row order) and the most items a call takes (NMP_IST_MAXITEMS)
+IST_NONE, IST_GT, IST_GE, IST_LT, IST_LE = 0, 1, 2, 3, 4
+IST_OPS = {"gt": IST_GT, "ge": IST_GE, "lt": IST_LT, "le": IST_LE}
+IST_MEAN, IST_DUR, IST_DEG, IST_SPELL = 1, 2, 4, 8
+IST_STATS = {"MEAN": IST_MEAN, "DUR": IST_DUR, "DEG": IST_DEG, "SPELL": IST_SPELL}
+IST_MAXITEMS = 32
+
 # spin-up drift (nmp_state_drift / nmp_drift_reduce): the tracked values'
 # rows (NMP_K_*: name -> first row) and the drift groups (NMP_G_*) with the
 # units of their drift

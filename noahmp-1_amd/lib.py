@@ -129,6 +129,11 @@ def load(build_if_missing: bool = False):
                                         C.c_int32, vp, vp, C.c_int64, vp]
     lib.nmp_extremes_output.argtypes = [vp, C.c_int64, C.c_int, i32p, C.c_double, vp, vp,
                                         C.c_int64, vp, C.c_int64, vp]
+    f64p = C.POINTER(C.c_double)
+    lib.nmp_intstats_update.argtypes = [vp, C.c_int64, C.c_int64, C.c_int, i32p, f64p, vp, vp, vp,
+                                        C.c_int32, vp, vp, C.c_int64, vp]
+    lib.nmp_intstats_output.argtypes = [vp, C.c_int64, C.c_int, i32p, C.c_int32, C.c_double, vp,
+                                        vp, C.c_int64, vp, C.c_int64, vp]
     lib.nmp_run.argtypes = [vp, C.c_int64, C.c_int64, f32p, C.c_float, C.c_float, C.c_int32,
                             C.c_int32, vp, vp, vp, vp, vp, C.c_int64, C.c_int32, vp, C.c_int, vp,
                             vp]
@@ -165,6 +170,7 @@ EXPORTED_SYMBOLS = ["nmp_read_tables", "nmp_init", "nmp_step", "nmp_step_binned"
                     "nmp_region_reduce", "nmp_state_output", "nmp_state_drift", "nmp_drift_reduce", "nmp_ldasin_regrid", "nmp_ldasin_downscale",
                     "nmp_ldasin_cosz", "nmp_forcing_from_ldasin_interp", "nmp_static_monthly",
                     "nmp_extremes_update", "nmp_extremes_output",
+                    "nmp_intstats_update", "nmp_intstats_output",
                     "nmp_run", "nmp_run_out", "nmp_frh2o", "nmp_frh2o_host", "nmp_calhum",
                     "nmp_calhum_host",
                     "nmp_state_from_aos", "nmp_sflx_columns", "nmp_sflx_column",

@@ -220,7 +220,7 @@ def _month_weighted(g12: np.ndarray, when: datetime.datetime) -> np.ndarray:
 
 # ---- state (initialization / restart) ----------------------------------------------
 def write_state(path: str, grid: Grid, state: np.ndarray, isnow: np.ndarray,
-                t: datetime.datetime, step: int = 0, accum=None, extremes=None):
+                t: datetime.datetime, step: int = 0, accum=None, extremes=None, intstats=None):
     """SoA state (56, n) + ISNOW on the grid; layer fields get a layer dimension.
     accum: (acc (NACC, n) float64, stor_beg (n,), steps) of an accumulating run
     part way through an output interval (driver.OfflineDriver(accumulate=True)),
@@ -231,7 +231,12 @@ def write_state(path: str, grid: Grid, state: np.ndarray, isnow: np.ndarray,
     run that tracks interval extremes (driver.OfflineDriver(extremes=...)),
     stored as variables EXT_<NAME>_MAX / _MIN in val's precision, EXTW_<NAME>_MAX
     / _MIN (int) and the global attributes extremes_steps and extremes_spec;
-    read_extremes reads them, read_state ignores them."""
+    read_extremes reads them, read_state ignores them.
+    intstats: (acc (nitems, n) float64, cnt (3*nitems, n) int32, steps, spec) of
+    a run that keeps interval statistics (driver.OfflineDriver(interval_stats=
+    ...)), stored as double variables IST_<LABEL>_SUM, int variables
+    IST_<LABEL>_COUNT / _RUN / _LONGEST and the global attributes intstats_steps
+    and intstats_spec; read_intstats reads them, read_state ignores them."""
     ny, nx = grid.shape
     f = netcdf_file(path, "w")
     try:
@@ -277,6 +282,19 @@ def write_state(path: str, grid: Grid, state: np.ndarray, isnow: np.ndarray,
                 v[:] = grid.scatter(vrow, np.asarray(FILL, xkind))
                 v = f.createVariable(f"EXTW_{name}", "i4", dims)
                 v[:] = grid.scatter(wrow.astype(np.int32), 0)
+        if intstats is not None:
+            acc, cnt, nsteps, spec = intstats
+            labels = _intstats_labels(spec)
+            assert acc.shape == (len(labels), grid.n) and cnt.shape == (3 * len(labels), grid.n), \
+                (acc.shape, cnt.shape)
+            f.intstats_steps = np.int32(nsteps)
+            f.intstats_spec = str(spec)
+            for i, label in enumerate(labels):
+                v = f.createVariable(f"IST_{label}_SUM", "f8", dims)
+                v[:] = grid.scatter(acc[i].astype(np.float64), np.float64(FILL))
+                for j, what in enumerate(_IST_COUNTERS):
+                    v = f.createVariable(f"IST_{label}_{what}", "i4", dims)
+                    v[:] = grid.scatter(cnt[3 * i + j].astype(np.int32), 0)
     finally:
         f.close()
 
@@ -301,6 +319,35 @@ def read_extremes(path: str, grid: Grid):
         val = np.stack([grid.columns(np.array(f.variables[f"EXT_{n}"][:])) for n in names])
         when = np.stack([grid.columns(np.array(f.variables[f"EXTW_{n}"][:])) for n in names])
         return val, when.astype(np.int32), int(f.extremes_steps), str(spec)
+    finally:
+        f.close()
+
+
+# the three counter rows of an interval-statistics item, in row order
+_IST_COUNTERS = ("COUNT", "RUN", "LONGEST")
+
+
+def _intstats_labels(spec: str) -> list:
+    """The labels of the spec's items: the rows of a run's running sums (and,
+    three to an item, of its counters)."""
+    from . import intstats as IS
+    return [it.label for it in IS.parse(spec)]
+
+
+def read_intstats(path: str, grid: Grid):
+    """(acc (nitems, n) float64, cnt (3*nitems, n) int32, steps, spec) of a
+    state file write_state stored a run's interval statistics in, or None when
+    the file carries none (an initialization file, a run without the option)."""
+    f = _read(path)
+    try:
+        if not hasattr(f, "intstats_steps") or not hasattr(f, "intstats_spec"):
+            return None
+        spec = f.intstats_spec.decode() if isinstance(f.intstats_spec, bytes) else f.intstats_spec
+        labels = _intstats_labels(spec)
+        acc = np.stack([grid.columns(np.array(f.variables[f"IST_{n}_SUM"][:])) for n in labels])
+        cnt = np.stack([grid.columns(np.array(f.variables[f"IST_{n}_{w}"][:]))
+                        for n in labels for w in _IST_COUNTERS])
+        return acc.astype(np.float64), cnt.astype(np.int32), int(f.intstats_steps), str(spec)
     finally:
         f.close()
 

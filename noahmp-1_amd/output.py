@@ -1,7 +1,8 @@
 """The output side of the offline driver (driver.OfflineDriver).
 
 An output file's rows come from producers with one interface, as the forcing
-comes from feeds (feeds._Feed): `Fluxes`, `Accumulation`, `Extremes`, `StateRows`.
+comes from feeds (feeds._Feed): `Fluxes`, `Accumulation`, `Extremes`, `IntervalStats`,
+`StateRows`.
 A producer has `names` (its rows), `needs_fluxes` (does it read the step's 16
 fluxes on every step) and `step(f, fluxes, rows)`: one more step with the
 forcing `f`, its fluxes in `fluxes` (None unless `needs_fluxes`) and, at an
@@ -22,7 +23,7 @@ from concurrent.futures import ThreadPoolExecutor
 import numpy as np
 import torch
 
-from . import extremes as X, layout as L, ncio, stateout
+from . import extremes as X, intstats as IS, layout as L, ncio, stateout
 
 
 def chain(hooks):
@@ -291,6 +292,65 @@ class Extremes:
         return hook
 
 
+class IntervalStats:
+    """An output interval's statistics (intstats.py), on the device: the running
+    sums `acc` of the selected items, their counters `cnt` (the steps a
+    condition held, its current and its longest run) and `k`, the steps taken
+    so far.  Only an item of the output fluxes makes every step write them."""
+    npz, nc = ("ist_acc", "ist_cnt", "ist_steps", "ist_spec"), ("intstats", ncio.read_intstats)
+
+    def __init__(self, engine, cs, items, dt: float):
+        self.engine, self.cs, self.dt, self.items = engine, cs, dt, list(items)
+        self.spec = IS.spec_string(self.items)
+        self.table, self.thresholds = IS.table(self.items), IS.thresholds(self.items)
+        self.names = IS.row_names(self.items)
+        self.needs_fluxes = IS.has_diag(self.items)
+        self.need_state = any(it.kind == L.EXT_SRC_STATE for it in self.items)
+        self.need_forcing = any(it.kind == L.EXT_SRC_FORCING for it in self.items)
+        n, dev = cs.ncol, cs.state.device
+        self.acc = torch.zeros((len(self.items), n), dtype=torch.float64, device=dev)
+        self.cnt = torch.zeros((3 * len(self.items), n), dtype=torch.int32, device=dev)
+        self.k = 0
+
+    def state(self):
+        """(acc, cnt, k, spec) of the interval so far, on the host: what a restart carries."""
+        return self.acc.cpu().numpy(), self.cnt.cpu().numpy(), self.k, self.spec
+
+    def restore(self, state, idx=slice(None)):
+        """`state` (state(), of the columns `idx` picks) resumes its interval
+        if it was taken with this run's spec; None, or another spec, starts a
+        fresh one: the next step is the interval's first and reads no old sum."""
+        self.k = 0
+        if state is None or str(state[3]) != self.spec:
+            return
+        dev = self.acc.device
+        self.acc.copy_(torch.as_tensor(np.ascontiguousarray(state[0][:, idx], np.float64),
+                                       device=dev))
+        self.cnt.copy_(torch.as_tensor(np.ascontiguousarray(state[1][:, idx], np.int32),
+                                       device=dev))
+        self.k = int(state[2])
+
+    def step(self, f, fluxes, rows):
+        """Fold this step into the running sums and counters from its fluxes
+        (None without a flux item), its forcing `f` and the state it left; at
+        an output step (rows: the output block's statistics rows) also form
+        the interval's rows, and the next step begins a new interval."""
+        self.k += 1
+        k = self.k
+        if rows is not None:
+            self.k = 0
+        state = self.cs.state if self.need_state else None
+        forcing = f if self.need_forcing else None
+
+        def hook(st, rng):
+            self.engine.intstats_update(self.table, self.thresholds, k, self.acc, self.cnt, fluxes,
+                                        forcing, state, stream=st, cols=rng)
+            if rows is not None:
+                self.engine.intstats_output(self.table, k, self.dt, self.acc, self.cnt, rows,
+                                            stream=st, cols=rng)
+        return hook
+
+
 class StateRows:
     """The selected groups of the land state (layout.STATE_OUT), formed at
     output steps from the state the step left (nmp_state_output), the groups
@@ -312,23 +372,31 @@ class StateRows:
 
 
 class OutputBlock:
-    """A run's producers in row order (fluxes, budget rows, extremes rows, state
-    rows) and what each step owes them.  `diag` is the (rows, ncol) block,
+    """A run's producers in row order (fluxes, budget rows, extremes rows,
+    interval-statistics rows, state rows) and what each step owes them.  `diag` is the (rows, ncol) block,
     `region_rows` the leading rows the regions reduce (None = all; state output
     ends them before the groups that can hold the fill value), `scratch` the one
     block the steps between output steps write their fluxes to (None unless a
     producer reads them), `carried` the producers a restart carries."""
 
-    def __init__(self, engine, cs, dt: float, accumulate: bool, ext_series, state_mask: int):
+    def __init__(self, engine, cs, dt: float, accumulate: bool, ext_series, state_mask: int,
+                 stat_items=None):
         self.accum = Accumulation(engine, cs, dt) if accumulate else None
         self.extremes = Extremes(engine, cs, ext_series, dt) if ext_series is not None else None
+        self.intstats = IntervalStats(engine, cs, stat_items, dt) if stat_items is not None \
+            else None
         state = StateRows(engine, cs, state_mask) if state_mask else None
-        self.producers = [p for p in (Fluxes(), self.accum, self.extremes, state) if p is not None]
-        self.carried = [p for p in (self.accum, self.extremes) if p is not None]
+        self.producers = [p for p in (Fluxes(), self.accum, self.extremes, self.intstats, state)
+                          if p is not None]
+        self.carried = [p for p in (self.accum, self.extremes, self.intstats) if p is not None]
         self.names, self.slices = [], []
         for p in self.producers:
             self.slices.append(slice(len(self.names), len(self.names) + len(p.names)))
             self.names += p.names
+        if self.intstats is not None and len(set(self.names)) != len(self.names):
+            twice = sorted({n for n in self.names if self.names.count(n) > 1})
+            raise ValueError(f"interval_stats: the row names {twice} occur twice in this run's "
+                             "output (choose another label)")
         self.region_rows = None if state is None else self.slices[-1].start + state.nofill_rows
         n, dev, dtype = cs.ncol, cs.state.device, cs.state.dtype
         self.diag = torch.zeros((len(self.names), n), dtype=dtype, device=dev)

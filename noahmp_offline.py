@@ -95,6 +95,16 @@ def build_parser():
                          "STC1..4), each with stats of max, min, tmax, tmin (default max+min), "
                          "e.g. T2M,TRAD:max,PRCP:max+tmax -- variables <NAME>_MAX, _MIN and the "
                          "seconds into the interval at which each occurred, _TMAX, _TMIN")
+    ap.add_argument("--interval-stats", default=None,
+                    metavar="[LABEL=]NAME[@OPc][:STAT[+STAT]][,...]",
+                    help="also write each output interval's statistics of the named series "
+                         "(the series of --extremes): without a condition the interval's mean, "
+                         "e.g. T2M,SMC1 -- variables T2M_MEAN, SMC1_MEAN; with a condition gt, "
+                         "ge, lt or le and a threshold, under a label, the seconds it held "
+                         "(dur, the default), its longest unbroken spell (spell) and the "
+                         "value-seconds beyond the threshold (deg), e.g. "
+                         "FROST=T2M@lt273.15:dur+spell,GDD=SFCTMP@gt278.15:deg -- variables "
+                         "FROST_DUR, FROST_SPELL, GDD_DEG")
     ap.add_argument("--regions", default=None, metavar="FILE",
                     help="netCDF cases: a region file on the run's grid (int REGION, optional "
                          "double AREA); every output time then also writes the regions' "
@@ -192,6 +202,13 @@ def main(argv=None):
         except ValueError as e:
             ap.error(str(e))
         skw.update(extremes=a.extremes)
+    if a.interval_stats is not None:
+        from noahmp_amd import intstats
+        try:
+            intstats.parse(a.interval_stats)
+        except ValueError as e:
+            ap.error(str(e))
+        skw.update(interval_stats=a.interval_stats)
     if os.path.isfile(cfg.constfile):
         rkw = dict(skw)
         if a.regions:

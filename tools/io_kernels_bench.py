@@ -45,6 +45,17 @@ achieved HBM bandwidth against their algorithmic bytes, at 1,048,576 columns.
                            nothing; with 4 and with 16 series
   extremes_output          every stat of every series: reads val and when
                            (16 B fp32, 24 B fp64 per series), writes 4 rows
+  intstats_update          a step past the interval's first, half of the items
+                           conditioned with a threshold that holds on about
+                           half of the columns: a mean item reads the value and
+                           reads and writes its double sum (20 B fp32, 24 B
+                           fp64); a conditioned one reads the value, the sum
+                           and three counters and writes the sum, the count and
+                           the run, rows counted whole (40 B fp32, 44 B fp64);
+                           with 4 and with 16 items
+  intstats_output          every stat of every item: a mean item reads its sum
+                           and writes 1 row, a conditioned one reads the sum
+                           and two counters and writes 3 rows
 
 The two gather/scatter kernels are timed with the grid points in the
 columns' own order (`point` = identity: coalesced) and fully shuffled (every
@@ -68,8 +79,8 @@ import numpy as np  # noqa: E402
 import torch  # noqa: E402
 
 import noahmp_pkg  # noqa: E402,F401
-from noahmp_amd import (cases as cases_mod, extremes as xtr, layout as L, spinup,  # noqa: E402
-                        stateout, timeman)
+from noahmp_amd import (cases as cases_mod, extremes as xtr, intstats as ist,  # noqa: E402
+                        layout as L, spinup, stateout, timeman)
 from noahmp_amd.engine import ColumnState, Engine  # noqa: E402
 from noahmp_amd.params import Params  # noqa: E402
 
@@ -245,6 +256,34 @@ def main():
                       ("extremes_output", f"{ns} series, 4 stats",
                        lambda masks=masks, xval=xval, xwhen=xwhen, xout=xout: eng.extremes_output(
                            masks, 900.0, xval, xwhen, xout), n * ns * (2 * (prec + 4) + 4 * prec))]
+        # interval statistics: half of the items means, half conditions that hold on
+        # about half of the columns (the blocks are standard normal; the state's
+        # rows have their medians as thresholds); primed by one call with k = 1
+        st = so_cs[prec].state
+        med = {x: float(st[ist.SOURCES[x][1]].double().median()) for x in
+               ("TG", "SNEQV", "SMC1", "STC1")}
+        for spec in ("T2M,TG,WARM=SFCTMP@gt0:dur+deg+spell,WET=PRCP@gt0:dur+deg+spell",
+                     "FSH,TRAD,T2M,ALBEDO,TG,SNEQV,SMC1,STC1,"
+                     + ",".join(f"C{i}={x}@{op}0:dur+deg+spell" for i, (x, op) in enumerate(
+                         [("FSH", "gt"), ("RUNSRF", "ge"), ("PRCP", "gt"), ("SFCTMP", "lt")]))
+                     + "," + ",".join(f"S{i}={x}@{op}{med[x]!r}:dur+deg+spell" for i, (x, op) in
+                                      enumerate([("TG", "gt"), ("SNEQV", "le"), ("SMC1", "lt"),
+                                                 ("STC1", "ge")]))):
+            items = ist.parse(spec)
+            ni, nc = len(items), sum(it.op != L.IST_NONE for it in items)
+            tab, thr = ist.table(items), ist.thresholds(items)
+            iacc = torch.zeros((ni, n), dtype=torch.float64, device=dev)
+            icnt = torch.zeros((3 * ni, n), dtype=torch.int32, device=dev)
+            iout = torch.empty((len(ist.row_names(items)), n), dtype=dt, device=dev)
+            eng.intstats_update(tab, thr, 1, iacc, icnt, diag, frc, st)
+            cases += [("intstats_update", f"{ni} items, {nc} conditioned",
+                       lambda tab=tab, thr=thr, iacc=iacc, icnt=icnt: eng.intstats_update(
+                           tab, thr, 2, iacc, icnt, diag, frc, st),
+                       n * ((ni - nc) * (prec + 16) + nc * (prec + 36))),
+                      ("intstats_output", f"{ni} items, every stat",
+                       lambda tab=tab, iacc=iacc, icnt=icnt, iout=iout: eng.intstats_output(
+                           tab, 12, 900.0, iacc, icnt, iout),
+                       n * ((ni - nc) * (8 + prec) + nc * (16 + 3 * prec)))]
         for name, order, fn, nbytes in cases:
             if only and name not in only:
                 continue

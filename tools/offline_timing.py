@@ -42,6 +42,10 @@ veg_clim="step", interleaved, reported the same way.
 --variants (default off,state,diag: without the option, with a spec of state
 and forcing series only, with a spec that has flux series and so writes the
 fluxes every step), interleaved with the order rotated, reported the same way.
+
+--interval-stats-runs N does the same for the interval statistics (variants
+off, state, diag: means and conditioned items of state and forcing series only,
+and a spec with flux items).
 """
 import argparse
 import json
@@ -278,22 +282,32 @@ EXTREMES_SPECS = {"state": "PRCP:max+tmax,SFCTMP,TG,SNEQV,SMC1,STC1",
                   "diag": "T2M,TRAD,FSH:max+tmax,RUNSRF:max+tmax,PRCP:max+tmax,TG"}
 
 
-def extremes_runs(a, nml):
+# --interval-stats-runs: likewise
+INTSTATS_SPECS = {"state": "TG,SNEQV,SMC1,STC1,FROST=SFCTMP@lt273.15:dur+spell+deg,"
+                           "WET=PRCP@gt0:dur+spell",
+                  "diag": "T2M,TRAD,TG,HEAT=FSH@gt0:deg,RUNOFF=RUNSRF@gt0:dur+spell,"
+                          "WET=PRCP@gt0:dur+spell"}
+
+
+def extremes_runs(a, nml, option="extremes", specs=None, count=None):
     """Fresh runs without extremes ("off"), with state and forcing series only
     ("state": the steps between output steps stay at DIAG_NONE) and with flux
     series ("diag": every step writes its fluxes), interleaved, the order
     rotated from round to round; ms per step of each run, and each variant's
     median and range.  "off" alone with --keep-case times this tree on a case
-    written before, next to another tree's runs on the same files."""
+    written before, next to another tree's runs on the same files.
+    option, specs, count: the same for another option of the driver that takes
+    a spec (interval_stats with INTSTATS_SPECS)."""
     if not (a.keep_case and os.path.exists(config.Config(nml).constfile)):
         import make_offline_case
         make_offline_case.main([nml, "--ny", str(a.ny), "--nx", str(a.nx), "--kind", "mixed"])
     cfg = config.Config(nml)
     names = [v for v in a.variants.split(",") if v]
     runs = {v: [] for v in names}
-    for i in range(a.extremes_runs):
+    specs = EXTREMES_SPECS if specs is None else specs
+    for i in range(a.extremes_runs if count is None else count):
         for name in names[i % len(names):] + names[:i % len(names)]:
-            kw = {} if name == "off" else dict(extremes=EXTREMES_SPECS[name])
+            kw = {} if name == "off" else {option: specs[name]}
             r, _, drv = time_driver(cfg, 4, True, a.warm, a.steps, a.threads, "device", True, **kw)
             r["variant"], r["round"] = name, i
             r["pcie_down_bytes_per_output_step"] = len(drv.out_names) * 4 * drv.cs.ncol
@@ -306,7 +320,7 @@ def extremes_runs(a, nml):
         summary[name] = {"runs": len(ms), "median_ms_per_step": float(np.median(ms)),
                          "min_ms_per_step": ms[0], "max_ms_per_step": ms[-1]}
         if name != "off":
-            summary[name]["spec"] = EXTREMES_SPECS[name]
+            summary[name]["spec"] = specs[name]
     print(json.dumps(summary), flush=True)
     return {"case": f"{a.ny} x {a.nx} land points (mixed USGS/STAS columns), 900-s steps, "
                     "hourly LDASIN, 3-hourly LDASOUT; fp32, file bytes ingested on the device; "
@@ -320,14 +334,19 @@ def main():
                     help="time N fresh runs each of --variants (off, state, diag: without "
                          "extremes, with state / forcing series, with flux series), interleaved, "
                          "instead")
+    ap.add_argument("--interval-stats-runs", type=int, default=0, metavar="N",
+                    help="the same for interval_stats: means and conditioned items of state / "
+                         "forcing series (state), with flux items (diag)")
     ap.add_argument("--veg-clim-runs", type=int, default=0, metavar="N",
                     help="time N fresh runs each without veg_clim and with veg_clim='step', "
                          "interleaved, instead")
     ap.add_argument("--variants", default=None, metavar="NAME[,NAME]",
                     help="with --veg-clim-runs: the variants to time (off, daily, step; default "
-                         "off,step); with --extremes-runs: off, state, diag (default all three)")
+                         "off,step); with --extremes-runs or --interval-stats-runs: off, state, "
+                         "diag (default all three)")
     ap.add_argument("--keep-case", action="store_true",
-                    help="with --veg-clim-runs or --extremes-runs: reuse the case files in "
+                    help="with --veg-clim-runs, --extremes-runs or --interval-stats-runs: reuse the "
+                         "case files in "
                          "--dir if they exist")
     ap.add_argument("--state-out-runs", type=int, default=0, metavar="N",
                     help="time N fresh runs each with and without state_out='all', interleaved, "
@@ -349,11 +368,14 @@ def main():
     os.makedirs(a.dir, exist_ok=True)
     nml = write_namelist(a.dir)
     if a.variants is None:
-        a.variants = "off,state,diag" if a.extremes_runs else "off,step"
-    if a.interp_runs or a.state_out_runs or a.veg_clim_runs or a.extremes_runs:
+        a.variants = "off,state,diag" if a.extremes_runs or a.interval_stats_runs else "off,step"
+    if a.interp_runs or a.state_out_runs or a.veg_clim_runs or a.extremes_runs or \
+            a.interval_stats_runs:
         res = (interp_runs(a, nml) if a.interp_runs else state_out_runs(a, nml)
                if a.state_out_runs else veg_clim_runs(a, nml) if a.veg_clim_runs
-               else extremes_runs(a, nml))
+               else extremes_runs(a, nml) if a.extremes_runs
+               else extremes_runs(a, nml, "interval_stats", INTSTATS_SPECS,
+                                  a.interval_stats_runs))
         if a.out:
             os.makedirs(os.path.dirname(os.path.abspath(a.out)), exist_ok=True)
             with open(a.out, "w") as f:
